@@ -20,6 +20,14 @@ torch.distributed (gloo) is used ONLY for rank rendezvous (worker-address
 exchange + barriers); the data plane is starway_amd itself.
 
 Rank 0 prints ONE JSON line with the aggregate result.
+
+A plain run only sets up, warms up, times ``--steps`` steps and prints the
+result line. ``--full`` adds the 64 B pingpong latency probes (asyncio and
+raw-callback API) after the timed region and reports them in ``config``.
+``--dump-outputs DIR`` writes what the last timed step delivered (each
+rank's receive buffers, or a fixed seeded sample of them) to
+``DIR/<name>.npy`` as float32; send payloads are seeded, so two builds run
+with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -63,14 +71,28 @@ def parse_args():
                         "steps complete inside the timed window (drained "
                         "before the closing sync/barrier).")
     p.add_argument("--lat-iters", type=int, default=200,
-                   help="64B pingpong iterations for the latency probe")
+                   help="64B pingpong iterations for the latency probe "
+                        "(runs only with --full)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the 64B pingpong latency probes after the "
+                        "timed steps (off by default: a plain run measures "
+                        "only the headline bandwidth)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write the buffers the last "
+                        "step delivered to DIR/<name>.npy (float32; a fixed "
+                        "seeded sample when they exceed the size budget)")
     p.add_argument("--device", default=None,
                    help="force 'cpu' or 'cuda' (default: auto)")
     p.add_argument("--transport", choices=("p2p", "rccl"), default="p2p",
                    help="p2p: starway tagged engine (hipIpc pulls); "
                         "rccl: ncclSend/ncclRecv all-to-all groups")
     p.add_argument("--json-out", default=None)
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
+    if args.warmup < 0:
+        p.error("--warmup must be >= 0")
+    return args
 
 
 def make_tag(src_rank: int, step: int, chunk: int = 0) -> int:
@@ -79,6 +101,54 @@ def make_tag(src_rank: int, step: int, chunk: int = 0) -> int:
 
 
 LAT_TAG_BASE = 1 << 59
+
+PAYLOAD_SEED = 0x5EED
+DUMP_SEED = 0xD0C5
+# --dump-outputs budget for the whole job, in float32 elements: 32 MiB of
+# .npy payload, split evenly over ranks and then over each rank's buffers.
+DUMP_MAX_ELEMS = 8 << 20
+
+
+def make_payload(n: int, src_rank: int, dst_rank: int, device: str):
+    """Seeded uint8 send payload for the (src, dst) pair: identical from run
+    to run for the same arguments, different for every pair and position so
+    a misrouted or shifted delivery shows up in the dumped outputs."""
+    seed = PAYLOAD_SEED + src_rank * 4099 + dst_rank
+    if device == "cpu":
+        return np.random.default_rng(seed).integers(0, 256, n, dtype=np.uint8)
+    import torch
+
+    g = torch.Generator(device="cuda")
+    g.manual_seed(seed)
+    return torch.randint(0, 256, (n,), dtype=torch.uint8, device="cuda",
+                         generator=g)
+
+
+def sample_indices(n: int, k: int):
+    """Sorted positions of the fixed seeded sample of an n-element buffer
+    that --dump-outputs keeps, or None when the whole buffer fits in k."""
+    if n <= k:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).integers(
+        0, n, k, dtype=np.int64))
+
+
+def dump_outputs(out_dir: str, named: dict, device: str, max_elems: int):
+    """Write each named 1-D uint8 buffer (or its seeded sample) as
+    out_dir/<name>.npy in float32."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    per_buf = max(1, max_elems // max(1, len(named)))
+    for name, buf in named.items():
+        idx = sample_indices(int(buf.shape[0]), per_buf)
+        if device == "cpu":
+            a = buf if idx is None else buf[idx]
+        else:
+            import torch
+
+            t = buf if idx is None else buf[torch.from_numpy(idx).cuda()]
+            a = t.cpu().numpy()
+        np.save(out / f"{name}.npy", a.astype(np.float32))
 
 
 async def run_rank(args, rank: int, world: int, device: str, dist):
@@ -131,7 +201,7 @@ async def run_rank(args, rank: int, world: int, device: str, dist):
 
     chunks = max(1, min(args.chunks, per_peer))
     bounds = [per_peer * k // chunks for k in range(chunks + 1)]
-    send_bufs = {j: alloc(per_peer, fill=(rank * 31 + j) % 251) for j in peers}
+    send_bufs = {j: make_payload(per_peer, rank, j, device) for j in peers}
     send_views = {j: [send_bufs[j][bounds[k]:bounds[k + 1]]
                       for k in range(chunks)] for j in peers}
     # Recv buffers are double-buffered by step parity so pipelined steps
@@ -163,7 +233,7 @@ async def run_rank(args, rank: int, world: int, device: str, dist):
                             device=torch.cuda.current_device())
         # all-to-all layout: peer-major chunks, msg_bytes per rank total.
         chunk = args.msg_bytes // world
-        rccl_send = alloc(chunk * world, fill=rank % 251)
+        rccl_send = make_payload(chunk * world, rank, world, device)
         rccl_recv = alloc(chunk * world)
         sync_device()
 
@@ -218,12 +288,27 @@ async def run_rank(args, rank: int, world: int, device: str, dist):
         elapsed = float(t.item())
         dist.barrier()
 
-    # ---- 64 B pingpong latency probe (rank0 <-> rank1, or loopback) ----
+    # ---- outputs of the last timed step (what a caller received) ----
+    if args.dump_outputs:
+        if mesh is not None:
+            named = {f"rank{rank}_alltoall_recv": rccl_recv}
+        else:
+            last = recv_bufs[(args.warmup + args.steps - 1) & 1]
+            named = {f"rank{rank}_recv_from{j}": last[j] for j in peers}
+        dump_outputs(args.dump_outputs, named, device,
+                     DUMP_MAX_ELEMS // world)
+        if world > 1:
+            dist.barrier()
+
+    # ---- 64 B pingpong latency probe (rank0 <-> rank1, or loopback);
+    # --full only ----
     half_rtt_us = None
     lat_samples = []
-    ping = alloc(64, fill=1)
-    pong = alloc(64)
-    if world == 1:
+    ping = alloc(64, fill=1) if args.full else None
+    pong = alloc(64) if args.full else None
+    if not args.full:
+        pass  # plain run: headline bandwidth only
+    elif world == 1:
         for i in range(args.lat_iters):
             t1 = time.perf_counter()
             fut = server.arecv(pong, LAT_TAG_BASE + i, full_mask)
@@ -250,7 +335,7 @@ async def run_rank(args, rank: int, world: int, device: str, dist):
     # with a GIL-yielding wait instead of an asyncio future — isolates the
     # event-loop wakeup cost from the transport cost.
     half_rtt_raw_us = None
-    if world == 1:
+    if args.full and world == 1:
         raw_samples = []
         for i in range(args.lat_iters):
             done: list = []
@@ -341,7 +426,7 @@ def main() -> int:
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+            "ms_per_step": round(elapsed / args.steps * 1e3, 6),
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,  # reference publishes no numbers
@@ -357,6 +442,7 @@ def main() -> int:
                 "device": device,
                 "transport": args.transport,
                 "parallelism": f"p2p-mesh{world}",
+                "full": args.full,
                 "pingpong_64B_half_rtt_us":
                     round(half_rtt_us, 2) if half_rtt_us else None,
                 "pingpong_64B_half_rtt_us_raw_api":

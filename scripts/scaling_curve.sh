@@ -14,11 +14,11 @@ for N in 1 2 4 8; do
     continue
   fi
   if [ "$N" -eq 1 ]; then
-    python bench.py --gpus 1 --steps "$STEPS" --warmup "$WARM" --msg-bytes "$MSG"
+    python bench.py --gpus 1 --steps "$STEPS" --warmup "$WARM" --msg-bytes "$MSG" --full
   else
     python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" \
       --master-addr 127.0.0.1 --master-port "$PORT" \
       bench.py --gpus "$N" --steps "$STEPS" --warmup "$WARM" --msg-bytes "$MSG" \
-      2>/dev/null | grep '"metric"'
+      --full 2>/dev/null | grep '"metric"'
   fi
 done

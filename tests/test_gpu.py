@@ -351,6 +351,36 @@ async def test_bench_loopback_step():
         assert torch.equal(src, dst)
 
 
+def test_bench_dump_outputs_matches_sent_payload(tmp_path):
+    """bench.py --dump-outputs on the device path: the dumped (sampled)
+    delivery of the last timed step equals the seeded payload that was
+    sent, and a plain run carries no latency probe."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    import bench
+
+    repo = Path(__file__).resolve().parent.parent
+    n = (16 << 20) + 13  # over the dump budget: exercises the sampled path
+    out = subprocess.run(
+        [sys.executable, str(repo / "bench.py"), "--gpus", "1", "--steps",
+         "3", "--warmup", "1", "--msg-bytes", str(n), "--dump-outputs",
+         str(tmp_path)],
+        capture_output=True, text=True, timeout=180, cwd=repo)
+    assert out.returncode == 0, out.stderr[-800:]
+    d = json.loads([l for l in out.stdout.splitlines()
+                    if l.startswith("{")][0])
+    assert d["config"]["device"] == "cuda" and d["steps"] == 3
+    assert d["config"]["pingpong_64B_half_rtt_us"] is None
+    got = np.load(tmp_path / "rank0_recv_from0.npy")
+    idx = bench.sample_indices(n, bench.DUMP_MAX_ELEMS)
+    assert got.dtype == np.float32 and got.shape == idx.shape
+    sent = bench.make_payload(n, 0, 0, "cuda").cpu().numpy()
+    assert np.array_equal(got, sent[idx].astype(np.float32))
+
+
 # =============================================================================
 # Strided (non-contiguous) device tensors: pack/unpack in the pull kernel
 # =============================================================================
