@@ -29,6 +29,8 @@
 
 #include <pybind11/pybind11.h>
 
+#include "copy_tuning.hpp"
+
 namespace py = pybind11;
 
 namespace sw {
@@ -749,8 +751,21 @@ void arm_leak(void* ticket);  // kernel may still write: do not reuse cell
 int poll_ticket(void* ticket, std::string* err);
 void free_ticket(void* ticket);
 void synchronize_all();
+// Test/bench hooks: synchronous copy-kernel launches on the pull stream.
+// A zero field in `tuning` / a zero block_cap means the default tuning.
+CopyTuning copy_tuning();  // the default; never touches the GPU
 bool copy_device_sync(void* dst, const void* src, size_t n, int device,
-                      std::string* err);
+                      const CopyTuning& tuning, std::string* err);
+bool copy_strided_sync(void* dst, uint64_t dst_stride, const void* src,
+                       uint64_t src_stride, uint64_t rows, uint64_t row_bytes,
+                       int device, size_t block_cap, std::string* err);
+struct CopyDesc {
+  void* dst;
+  const void* src;
+  uint64_t bytes;
+};
+bool copy_multi_sync(const CopyDesc* descs, int n, int device,
+                     std::string* err);
 // Stats for evaluate_perf / transports introspection. Values come from a
 // cached on-box copy microbenchmark (~/.cache/starway/perf.cal) with
 // round-1 measurements as analytic fallback.

@@ -33,6 +33,12 @@ hipError_t launch_copy_strided(void* dst, uint64_t dst_stride,
                                const void* src, uint64_t src_stride,
                                uint64_t rows, uint64_t row_bytes,
                                hipStream_t stream);
+hipError_t launch_copy_tuned(void* dst, const void* src, size_t bytes,
+                             hipStream_t stream, const CopyTuning& t);
+hipError_t launch_copy_strided_tuned(void* dst, uint64_t dst_stride,
+                                     const void* src, uint64_t src_stride,
+                                     uint64_t rows, uint64_t row_bytes,
+                                     hipStream_t stream, const CopyTuning& t);
 
 namespace gpu {
 
@@ -713,34 +719,75 @@ void free_ticket(void* ticket) {
   delete t;
 }
 
-// Synchronous device copy through the gfx950 copy kernel (test/bench hook).
-bool copy_device_sync(void* dst, const void* src, size_t n, int device,
-                      std::string* err) {
+// ---------------------------------------------------------------------------
+// Test/bench hooks: synchronous launches of the copy kernels on the pull
+// stream, optionally with an explicit tuning (0 in a field = the default).
+// ---------------------------------------------------------------------------
+
+CopyTuning copy_tuning() { return default_copy_tuning(); }
+
+static CopyTuning resolve_tuning(const CopyTuning& t) {
+  CopyTuning r = default_copy_tuning();
+  if (t.block_cap) r.block_cap = t.block_cap;
+  if (t.nt_threshold) r.nt_threshold = t.nt_threshold;
+  if (t.nt_unroll) r.nt_unroll = t.nt_unroll;
+  return r;
+}
+
+// Take g_mu, switch to `device`, run `launch` on its pull stream and wait.
+template <class Launch>
+static bool run_sync(int device, std::string* err, Launch launch) {
   if (!available()) {
     *err = "no HIP device";
     return false;
   }
-  hipStream_t stream;
-  {
-    std::lock_guard<std::mutex> lk(g_mu);
-    int prev;
-    hipGetDevice(&prev);
-    hipSetDevice(device);
-    stream = pull_stream(device);
-    hipError_t e = launch_copy(dst, src, n, stream);
-    if (e != hipSuccess) {
-      hipSetDevice(prev);
-      *err = hipGetErrorString(e);
-      return false;
-    }
-    e = hipStreamSynchronize(stream);
-    hipSetDevice(prev);
-    if (e != hipSuccess) {
-      *err = hipGetErrorString(e);
-      return false;
-    }
+  std::lock_guard<std::mutex> lk(g_mu);
+  int prev;
+  hipGetDevice(&prev);
+  hipSetDevice(device);
+  hipStream_t stream = pull_stream(device);
+  hipError_t e = launch(stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  hipSetDevice(prev);
+  if (e != hipSuccess) {
+    *err = hipGetErrorString(e);
+    return false;
   }
   return true;
+}
+
+bool copy_device_sync(void* dst, const void* src, size_t n, int device,
+                      const CopyTuning& tuning, std::string* err) {
+  CopyTuning t = resolve_tuning(tuning);
+  return run_sync(device, err, [&](hipStream_t stream) {
+    return launch_copy_tuned(dst, src, n, stream, t);
+  });
+}
+
+bool copy_strided_sync(void* dst, uint64_t dst_stride, const void* src,
+                       uint64_t src_stride, uint64_t rows, uint64_t row_bytes,
+                       int device, size_t block_cap, std::string* err) {
+  CopyTuning t = resolve_tuning(CopyTuning{block_cap, 0, 0});
+  return run_sync(device, err, [&](hipStream_t stream) {
+    return launch_copy_strided_tuned(dst, dst_stride, src, src_stride, rows,
+                                     row_bytes, stream, t);
+  });
+}
+
+// Callers validate 1 <= n <= 8 and bytes < 2^32 (launch_copy_multi does not).
+bool copy_multi_sync(const CopyDesc* descs, int n, int device,
+                     std::string* err) {
+  if (n < 1 || n > 8) {
+    *err = "copy_multi_sync: bad batch size";
+    return false;
+  }
+  MultiCopyDesc d[8];
+  for (int i = 0; i < n; i++)
+    d[i] = {(const uint8_t*)descs[i].src, (uint8_t*)descs[i].dst,
+            (uint32_t)descs[i].bytes};
+  return run_sync(device, err, [&](hipStream_t stream) {
+    return launch_copy_multi(d, n, stream);
+  });
 }
 
 void synchronize_all() {

@@ -38,7 +38,18 @@ void attach_bounce(void*, RawBuf&&) {}
 int poll_ticket(void*, std::string*) { return -1; }
 void free_ticket(void*) {}
 void synchronize_all() {}
-bool copy_device_sync(void*, const void*, size_t, int, std::string* err) {
+CopyTuning copy_tuning() { return CopyTuning{8192, (size_t)64 << 20, 4}; }
+bool copy_device_sync(void*, const void*, size_t, int, const CopyTuning&,
+                      std::string* err) {
+  *err = "no GPU (sanitizer stub)";
+  return false;
+}
+bool copy_strided_sync(void*, uint64_t, const void*, uint64_t, uint64_t,
+                       uint64_t, int, size_t, std::string* err) {
+  *err = "no GPU (sanitizer stub)";
+  return false;
+}
+bool copy_multi_sync(const CopyDesc*, int, int, std::string* err) {
   *err = "no GPU (sanitizer stub)";
   return false;
 }

@@ -20,6 +20,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdlib>
+
+#include "copy_tuning.hpp"
 
 namespace sw {
 
@@ -202,22 +205,36 @@ hipError_t launch_copy_multi(const MultiCopyDesc* descs, int n,
 // Host-side dispatch
 // ---------------------------------------------------------------------------
 
-static inline int copy_grid(size_t work_items) {
-  // >> 256 WGs to fill 8 XCDs x 32 CUs; cap so tiny copies stay one-wave-ish.
-  // Cap tunable via STARWAY_COPY_BLOCKS for on-box sweeps.
-  static const size_t cap = [] {
+const CopyTuning& default_copy_tuning() {
+  // Read once per process; STARWAY_COPY_BLOCKS / STARWAY_NT_THRESHOLD /
+  // STARWAY_COPY_UNROLL exist for on-box sweeps (scripts/copy_tune.sh).
+  static const CopyTuning t = [] {
+    CopyTuning d;
     const char* v = getenv("STARWAY_COPY_BLOCKS");
-    return v && *v ? strtoull(v, nullptr, 10) : 8192ull;
+    d.block_cap = v && *v ? (size_t)strtoull(v, nullptr, 10) : (size_t)8192;
+    // NT past 64 MiB: the copy would otherwise sweep the 256 MiB LLC.
+    v = getenv("STARWAY_NT_THRESHOLD");
+    d.nt_threshold =
+        v && *v ? (size_t)strtoull(v, nullptr, 10) : (size_t)64 << 20;
+    v = getenv("STARWAY_COPY_UNROLL");
+    d.nt_unroll = v && *v ? atoi(v) : 4;
+    return d;
   }();
+  return t;
+}
+
+static inline int copy_grid(size_t work_items, size_t cap) {
+  // >> 256 WGs to fill 8 XCDs x 32 CUs; cap so tiny copies stay one-wave-ish.
   size_t blocks = (work_items + 255) / 256;
   if (blocks < 1) blocks = 1;
   if (blocks > cap) blocks = cap;
   return (int)blocks;
 }
 
-hipError_t launch_copy(void* dst, const void* src, size_t bytes,
-                       hipStream_t stream) {
+hipError_t launch_copy_tuned(void* dst, const void* src, size_t bytes,
+                             hipStream_t stream, const CopyTuning& t) {
   if (bytes == 0) return hipSuccess;
+  const size_t cap = t.block_cap;
   uintptr_t s = (uintptr_t)src, d = (uintptr_t)dst;
   if ((s & 15) == (d & 15)) {
     // Co-aligned: byte head to the next 16B boundary, vector bulk, byte tail.
@@ -233,28 +250,18 @@ hipError_t launch_copy(void* dst, const void* src, size_t bytes,
     size_t n16 = bytes / 16;
     size_t tail = bytes & 15;
     if (n16) {
-      // NT past 64 MiB (STARWAY_NT_THRESHOLD): the copy would otherwise
-      // sweep the 256 MiB LLC.
-      static const size_t kNtThreshold = [] {
-        const char* v = getenv("STARWAY_NT_THRESHOLD");
-        return v && *v ? (size_t)strtoull(v, nullptr, 10) : (size_t)64 << 20;
-      }();
-      static const int nt_unroll = [] {
-        const char* v = getenv("STARWAY_COPY_UNROLL");
-        return v && *v ? atoi(v) : 4;
-      }();
-      if (bytes >= kNtThreshold) {
-        if (nt_unroll >= 8) {
-          hipLaunchKernelGGL(k_copy_b128_nt_u8, dim3(copy_grid(n16 / 8 + 1)),
-                             dim3(256), 0, stream, (const u32x4*)s,
-                             (u32x4*)d, n16);
+      if (bytes >= t.nt_threshold) {
+        if (t.nt_unroll >= 8) {
+          hipLaunchKernelGGL(k_copy_b128_nt_u8,
+                             dim3(copy_grid(n16 / 8 + 1, cap)), dim3(256), 0,
+                             stream, (const u32x4*)s, (u32x4*)d, n16);
         } else {
-          hipLaunchKernelGGL(k_copy_b128_nt, dim3(copy_grid(n16 / 4 + 1)),
-                             dim3(256), 0, stream, (const u32x4*)s,
-                             (u32x4*)d, n16);
+          hipLaunchKernelGGL(k_copy_b128_nt,
+                             dim3(copy_grid(n16 / 4 + 1, cap)), dim3(256), 0,
+                             stream, (const u32x4*)s, (u32x4*)d, n16);
         }
       } else {
-        hipLaunchKernelGGL(k_copy_b128, dim3(copy_grid(n16 / 4 + 1)),
+        hipLaunchKernelGGL(k_copy_b128, dim3(copy_grid(n16 / 4 + 1, cap)),
                            dim3(256), 0, stream, (const uint4*)s, (uint4*)d,
                            n16);
       }
@@ -266,11 +273,45 @@ hipError_t launch_copy(void* dst, const void* src, size_t bytes,
     }
   } else if ((s & 3) == (d & 3) && (s & 3) == 0 && (bytes & 3) == 0) {
     size_t n4 = bytes / 4;
-    hipLaunchKernelGGL(k_copy_b32, dim3(copy_grid(n4 / 4 + 1)), dim3(256), 0,
-                       stream, (const uint32_t*)src, (uint32_t*)dst, n4);
+    hipLaunchKernelGGL(k_copy_b32, dim3(copy_grid(n4 / 4 + 1, cap)),
+                       dim3(256), 0, stream, (const uint32_t*)src,
+                       (uint32_t*)dst, n4);
   } else {
-    hipLaunchKernelGGL(k_copy_b8, dim3(copy_grid(bytes / 16 + 1)), dim3(256),
-                       0, stream, (const uint8_t*)src, (uint8_t*)dst, bytes);
+    hipLaunchKernelGGL(k_copy_b8, dim3(copy_grid(bytes / 16 + 1, cap)),
+                       dim3(256), 0, stream, (const uint8_t*)src,
+                       (uint8_t*)dst, bytes);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_copy(void* dst, const void* src, size_t bytes,
+                       hipStream_t stream) {
+  return launch_copy_tuned(dst, src, bytes, stream, default_copy_tuning());
+}
+
+hipError_t launch_copy_strided_tuned(void* dst, uint64_t dst_stride,
+                                     const void* src, uint64_t src_stride,
+                                     uint64_t rows, uint64_t row_bytes,
+                                     hipStream_t stream,
+                                     const CopyTuning& t) {
+  if (rows == 0 || row_bytes == 0) return hipSuccess;
+  const size_t cap = t.block_cap;
+  uintptr_t s = (uintptr_t)src, d = (uintptr_t)dst;
+  bool vec = (s & 15) == 0 && (d & 15) == 0 && (src_stride & 15) == 0 &&
+             (dst_stride & 15) == 0 && (row_bytes & 15) == 0;
+  if (vec) {
+    uint64_t row_n16 = row_bytes / 16;
+    size_t total = (size_t)rows * row_n16;
+    hipLaunchKernelGGL(k_copy_strided_b128,
+                       dim3(copy_grid(total / 4 + 1, cap)), dim3(256), 0,
+                       stream, (const uint8_t*)src, src_stride, (uint8_t*)dst,
+                       dst_stride, rows, row_n16);
+  } else {
+    size_t total = (size_t)rows * row_bytes;
+    hipLaunchKernelGGL(k_copy_strided_b8,
+                       dim3(copy_grid(total / 16 + 1, cap)), dim3(256), 0,
+                       stream, (const uint8_t*)src, src_stride, (uint8_t*)dst,
+                       dst_stride, rows, row_bytes);
   }
   return hipGetLastError();
 }
@@ -279,23 +320,8 @@ hipError_t launch_copy_strided(void* dst, uint64_t dst_stride,
                                const void* src, uint64_t src_stride,
                                uint64_t rows, uint64_t row_bytes,
                                hipStream_t stream) {
-  if (rows == 0 || row_bytes == 0) return hipSuccess;
-  uintptr_t s = (uintptr_t)src, d = (uintptr_t)dst;
-  bool vec = (s & 15) == 0 && (d & 15) == 0 && (src_stride & 15) == 0 &&
-             (dst_stride & 15) == 0 && (row_bytes & 15) == 0;
-  if (vec) {
-    uint64_t row_n16 = row_bytes / 16;
-    size_t total = (size_t)rows * row_n16;
-    hipLaunchKernelGGL(k_copy_strided_b128, dim3(copy_grid(total / 4 + 1)),
-                       dim3(256), 0, stream, (const uint8_t*)src, src_stride,
-                       (uint8_t*)dst, dst_stride, rows, row_n16);
-  } else {
-    size_t total = (size_t)rows * row_bytes;
-    hipLaunchKernelGGL(k_copy_strided_b8, dim3(copy_grid(total / 16 + 1)),
-                       dim3(256), 0, stream, (const uint8_t*)src, src_stride,
-                       (uint8_t*)dst, dst_stride, rows, row_bytes);
-  }
-  return hipGetLastError();
+  return launch_copy_strided_tuned(dst, dst_stride, src, src_stride, rows,
+                                   row_bytes, stream, default_copy_tuning());
 }
 
 }  // namespace sw

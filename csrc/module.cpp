@@ -316,18 +316,74 @@ PYBIND11_MODULE(_core, m) {
     py::gil_scoped_release rel;
     gpu::ipc_close_all();
   });
-  // Test/bench hook: run the gfx950 copy kernel dst<-src synchronously.
+  // Test/bench hooks: run the gfx950 copy kernels synchronously on raw
+  // device pointers. Tuning arguments of 0 mean the process default
+  // (_copy_tuning()); explicit values let one process reach every kernel
+  // variant and a capped (multi-iteration) grid at small sizes.
   m.def("_copy_device_sync",
-        [](uintptr_t dst, uintptr_t src, size_t nbytes, int device) {
+        [](uintptr_t dst, uintptr_t src, size_t nbytes, int device,
+           size_t block_cap, size_t nt_threshold, int nt_unroll) {
           std::string err;
           bool ok;
           {
             py::gil_scoped_release rel;
-            ok = gpu::copy_device_sync((void*)dst, (const void*)src, nbytes,
-                                       device, &err);
+            ok = gpu::copy_device_sync(
+                (void*)dst, (const void*)src, nbytes, device,
+                CopyTuning{block_cap, nt_threshold, nt_unroll}, &err);
           }
           if (!ok) throw std::runtime_error("copy_device_sync: " + err);
         },
-        py::arg("dst"), py::arg("src"), py::arg("nbytes"), py::arg("device"));
+        py::arg("dst"), py::arg("src"), py::arg("nbytes"), py::arg("device"),
+        py::arg("block_cap") = 0, py::arg("nt_threshold") = 0,
+        py::arg("nt_unroll") = 0);
+  m.def("_copy_strided_sync",
+        [](uintptr_t dst, uint64_t dst_stride, uintptr_t src,
+           uint64_t src_stride, uint64_t rows, uint64_t row_bytes, int device,
+           size_t block_cap) {
+          std::string err;
+          bool ok;
+          {
+            py::gil_scoped_release rel;
+            ok = gpu::copy_strided_sync((void*)dst, dst_stride,
+                                        (const void*)src, src_stride, rows,
+                                        row_bytes, device, block_cap, &err);
+          }
+          if (!ok) throw std::runtime_error("copy_strided_sync: " + err);
+        },
+        py::arg("dst"), py::arg("dst_stride"), py::arg("src"),
+        py::arg("src_stride"), py::arg("rows"), py::arg("row_bytes"),
+        py::arg("device"), py::arg("block_cap") = 0);
+  // descs: list of (dst, src, nbytes); one k_copy_multi launch.
+  m.def("_copy_multi_sync",
+        [](const std::vector<std::tuple<uintptr_t, uintptr_t, uint64_t>>&
+               descs,
+           int device) {
+          if (descs.empty() || descs.size() > 8)
+            throw py::value_error("copy_multi_sync: need 1..8 descriptors");
+          gpu::CopyDesc d[8];
+          for (size_t i = 0; i < descs.size(); i++) {
+            auto [dst, src, nbytes] = descs[i];
+            if (nbytes >= (1ull << 32))
+              throw py::value_error(
+                  "copy_multi_sync: descriptor size must be < 2**32");
+            d[i] = {(void*)dst, (const void*)src, nbytes};
+          }
+          std::string err;
+          bool ok;
+          {
+            py::gil_scoped_release rel;
+            ok = gpu::copy_multi_sync(d, (int)descs.size(), device, &err);
+          }
+          if (!ok) throw std::runtime_error("copy_multi_sync: " + err);
+        },
+        py::arg("descs"), py::arg("device"));
+  m.def("_copy_tuning", [] {
+    CopyTuning t = gpu::copy_tuning();
+    py::dict d;
+    d["block_cap"] = t.block_cap;
+    d["nt_threshold"] = t.nt_threshold;
+    d["nt_unroll"] = t.nt_unroll;
+    return d;
+  });
   m.attr("__version__") = "0.1.0";
 }

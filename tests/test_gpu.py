@@ -869,3 +869,196 @@ async def test_small_device_send_with_inbox_disabled(port):
             p.join()
         p.close()
         await server.aclose()
+
+
+# =============================================================================
+# Data-plane selection and exactness through the engine, guard-banded
+# (tests/_guard.py: whole destination arena compared with a numpy
+# expectation, source arena unchanged)
+# =============================================================================
+
+from _guard import GuardedCopy, Region  # noqa: E402
+
+INBOX_OFFSETS = [(s, d) for s in (0, 1, 8) for d in (0, 3)]
+
+
+@pytest.mark.parametrize("nbytes", [1, 15, 16, 17, 4095, 4096])
+async def test_inbox_boundary_sizes_and_alignments(nbytes):
+    """Ring plane up to its 4096 B slot payload: the push kernel's
+    src-alignment branch and the unpack kernel's dst-alignment branch,
+    each with %16 and odd sizes."""
+    async with loopback() as (server, client):
+        cases = [GuardedCopy(7000 + nbytes * 8 + k, Region.flat(so, nbytes),
+                             Region.flat(do, nbytes))
+                 for k, (so, do) in enumerate(INBOX_OFFSETS)]
+        await asyncio.sleep(0.3)  # cold-start probe settle (stats asserts)
+        for k, case in enumerate(cases):
+            tx0 = client._client.get_stats()["inbox_tx"]
+            rx0 = server._server.get_stats()["inbox_rx"]
+            fut = server.arecv(case.dst_view, 0, 0)
+            await asyncio.sleep(0.01)
+            await client.asend(case.src_view, 20 + k)
+            tag, length = await fut
+            assert tag == 20 + k and length == nbytes
+            case.check(f"inbox {nbytes} B src+{case.src.off} "
+                       f"dst+{case.dst.off}")
+            assert client._client.get_stats()["inbox_tx"] == tx0 + 1
+            assert server._server.get_stats()["inbox_rx"] == rx0 + 1
+
+
+async def test_first_size_past_inbox_rides_rts_plane():
+    """4097 B does not fit a ring slot: RTS + pull kernel, not the ring."""
+    nbytes = 4097
+    async with loopback() as (server, client):
+        cases = [GuardedCopy(7100 + k, Region.flat(so, nbytes),
+                             Region.flat(do, nbytes))
+                 for k, (so, do) in enumerate(INBOX_OFFSETS)]
+        await asyncio.sleep(0.3)  # ring active: the size alone decides
+        for k, case in enumerate(cases):
+            tx0 = client._client.get_stats()["inbox_tx"]
+            rx0 = server._server.get_stats()["gpu_rx"]
+            fut = server.arecv(case.dst_view, 0, 0)
+            await asyncio.sleep(0.01)
+            await client.asend(case.src_view, 40 + k)
+            tag, length = await fut
+            assert tag == 40 + k and length == nbytes
+            case.check(f"rts 4097 B src+{case.src.off} dst+{case.dst.off}")
+            assert client._client.get_stats()["inbox_tx"] == tx0
+            assert server._server.get_stats()["gpu_rx"] == rx0 + 1
+
+
+async def test_batched_small_pulls_exact():
+    """Eleven concurrent RTS-plane messages (one batch of 8 and a
+    remainder when the engine sees them together; singly otherwise --
+    either way every destination arena must be exact)."""
+    sizes = [4097, 8191, 8192, 65535, 65536]
+    offs = [(0, 0), (1, 0), (0, 3), (8, 8), (5, 9), (0, 15)]
+    async with loopback() as (server, client):
+        cases = []
+        for i in range(11):
+            n = sizes[i % len(sizes)]
+            so, do = offs[i % len(offs)]
+            cases.append(GuardedCopy(7200 + i, Region.flat(so, n),
+                                     Region.flat(do, n)))
+        recvs = [server.arecv(c.dst_view, 300 + i, (1 << 64) - 1)
+                 for i, c in enumerate(cases)]
+        await asyncio.sleep(0.01)
+        sends = [client.asend(c.src_view, 300 + i)
+                 for i, c in enumerate(cases)]
+        got = await asyncio.gather(*recvs)
+        await asyncio.gather(*sends)
+        for i, (c, (tag, length)) in enumerate(zip(cases, got)):
+            assert tag == 300 + i and length == c.src.nbytes
+            c.check(f"batched pull {i}: {c.src.nbytes} B")
+
+
+def _random_typed(seed, shape, dtype):
+    """CPU tensor of `dtype` whose bytes are a seeded random stream (bit
+    patterns, NaNs included: comparisons below are on the bytes)."""
+    es = torch.empty((), dtype=dtype).element_size()
+    raw = np.random.default_rng(seed).integers(
+        0, 256, shape[0] * shape[1] * es, dtype=np.uint8)
+    return torch.from_numpy(raw).view(dtype).reshape(shape)
+
+
+def _bytes(t):
+    return t.contiguous().cpu().view(torch.uint8).numpy()
+
+
+@pytest.mark.parametrize(
+    "dtype,shape,cols",
+    [
+        # 12 B column offset: misaligned rows, k_copy_strided_b8
+        pytest.param(torch.float32, (32, 64), (3, 35),
+                     id="float32-k_copy_strided_b8"),
+        # 16 B column offset, 256 B stride: k_copy_strided_b128
+        pytest.param(torch.bfloat16, (24, 128), (8, 72),
+                     id="bfloat16-k_copy_strided_b128"),
+        pytest.param(torch.int64, (9, 40), (1, 33),
+                     id="int64-k_copy_strided_b8"),
+    ])
+async def test_strided_elements_wider_than_a_byte(dtype, shape, cols):
+    """Row-strided slices of 4-, 2- and 8-byte elements: the facade scales
+    row length and stride by the element size. Reference: torch's
+    .contiguous() of the same slice of the CPU copy of the base."""
+    a, b = cols
+    base_cpu = _random_typed(7300 + shape[0], shape, dtype)
+    expect = base_cpu[:, a:b].contiguous()
+    async with loopback() as (server, client):
+        # strided source -> contiguous destination
+        base = base_cpu.cuda()
+        dst = torch.zeros(expect.shape, dtype=dtype, device="cuda")
+        torch.cuda.synchronize()
+        fut = server.arecv(dst, 0, 0)
+        await client.asend(base[:, a:b], 60)
+        tag, length = await fut
+        torch.cuda.synchronize()
+        assert tag == 60 and length == expect.numel() * expect.element_size()
+        assert np.array_equal(_bytes(dst), _bytes(expect))
+        assert np.array_equal(_bytes(base), _bytes(base_cpu))
+
+        # contiguous source -> strided destination window
+        frame_cpu = _random_typed(7400 + shape[0], shape, dtype)
+        fb = frame_cpu.view(torch.uint8).numpy()  # shares memory
+        eb = _bytes(expect).reshape(shape[0], -1)
+        es = expect.element_size()
+        window = fb.reshape(shape[0], -1)[:, a * es:b * es]
+        window[window == eb] ^= 0xFF  # an unwritten byte never matches
+        frame_expect = frame_cpu.clone()
+        frame_expect[:, a:b] = expect
+        frame = frame_cpu.cuda()
+        src = expect.cuda()
+        torch.cuda.synchronize()
+        fut = server.arecv(frame[:, a:b], 0, 0)
+        await asyncio.sleep(0.01)
+        await client.asend(src, 61)
+        tag, length = await fut
+        torch.cuda.synchronize()
+        assert tag == 61 and length == expect.numel() * es
+        assert np.array_equal(_bytes(frame), _bytes(frame_expect))
+
+
+async def test_contiguous_send_to_strided_recv_above_inbox_size():
+    """48 x 192 B (9216 B: cannot ride the ring) into frame[:, 37:229] of
+    a 48 x 300 frame: contiguous source, strided destination, through the
+    pull kernel (column offset 37: k_copy_strided_b8). Gaps keep their
+    prefill."""
+    case = GuardedCopy(7500, Region.flat(0, 48 * 192),
+                       Region(37, 48, 192, 300))
+    async with loopback() as (server, client):
+        rx0 = server._server.get_stats()["gpu_rx"]
+        fut = server.arecv(case.dst_view, 0, 0)
+        await asyncio.sleep(0.01)
+        await client.asend(case.src_view, 62)
+        tag, length = await fut
+        assert tag == 62 and length == 48 * 192
+        case.check("contiguous -> strided window")
+        assert server._server.get_stats()["gpu_rx"] == rx0 + 1
+
+
+async def test_strided_device_to_host_recv():
+    """A 20 x 96 slice of a 20 x 160 device frame into a numpy buffer:
+    the 2-D device-to-host copy of the pull path."""
+    case = GuardedCopy(7600, Region(32, 20, 96, 160),
+                       Region.flat(0, 20 * 96), dst_on_host=True)
+    async with loopback() as (server, client):
+        fut = server.arecv(case.dst_view, 0, 0)
+        await asyncio.sleep(0.01)
+        await client.asend(case.src_view, 63)
+        tag, length = await fut
+        assert tag == 63 and length == 20 * 96
+        case.check("strided device -> host")
+
+
+async def test_host_send_to_strided_device_recv():
+    """A numpy source into a 20 x 96 window of a 20 x 160 device frame:
+    the 2-D host-to-device upload."""
+    case = GuardedCopy(7700, Region.flat(0, 20 * 96),
+                       Region(32, 20, 96, 160), src_on_host=True)
+    async with loopback() as (server, client):
+        fut = server.arecv(case.dst_view, 0, 0)
+        await asyncio.sleep(0.01)
+        await client.asend(case.src_view, 64)
+        tag, length = await fut
+        assert tag == 64 and length == 20 * 96
+        case.check("host -> strided device window")
