@@ -17,7 +17,10 @@ CSRC = REPO / "csrc"
 BUILD = REPO / "build"
 PKG = REPO / "starway_amd"
 
-SOURCES = ["engine.cpp", "gpu.cpp", "module.cpp", "kernels.hip", "smallmsg.hip"]
+ENGINE_SOURCES = ["engine.cpp", "engine_wire.cpp", "engine_match.cpp",
+                  "engine_planes.cpp"]
+SOURCES = [*ENGINE_SOURCES, "gpu.cpp", "module.cpp", "kernels.hip",
+           "smallmsg.hip"]
 RCCL_SOURCES = ["rccl_group.cpp"]
 
 HIPCC = os.environ.get("STARWAY_HIPCC", "hipcc")
@@ -140,7 +143,7 @@ def build_sanitizer(kind: str = "thread", verbose: bool = True) -> Path:
         "g++", "-O1", "-g", "-std=c++20", f"-fsanitize={kind}",
         "-fno-omit-frame-pointer",
         "-I", str(CSRC), "-I", py_inc, "-I", _pybind11_include(),
-        str(CSRC / "engine.cpp"), str(CSRC / "gpu_stub.cpp"),
+        *[str(CSRC / s) for s in ENGINE_SOURCES], str(CSRC / "gpu_stub.cpp"),
         str(CSRC / "sanitizer_stress_main.cpp"),
         f"-L{libdir}", f"-lpython{pyver}", "-lpthread", "-o", str(out),
     ]

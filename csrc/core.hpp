@@ -301,7 +301,7 @@ struct UnexpectedMsg {
   uint8_t* redirect_dst = nullptr;
 };
 
-class ShmChannel;  // shm.hpp (engine.cpp only)
+class ShmChannel;  // shm.hpp (engine*.cpp only)
 
 struct Connection {
   int fd = -1;
@@ -490,6 +490,29 @@ class Engine {
   void fire_completions();  // acquires GIL, drains completions_
   void complete(Completion&& comp);
   void fail_op(Op* op, const std::string& reason);
+  // Which counters a delivered recv bumps besides msgs/bytes_received.
+  // None counts nothing at all (mid-stream redirect, see deliver_recv).
+  enum class RxPlane : uint8_t { None, Eager, Gpu, Cma, Inbox, Doorbell };
+  void deliver_recv(Op* r, uint64_t tag, uint64_t len, RxPlane plane);
+  void complete_send(Op* op);
+  void complete_flush(Op* f);
+  // Tell a rendezvous sender its message was refused (no-op without a
+  // sender op or on a dead connection); reject_rndv also fails the recv.
+  void send_recv_fail(Connection* c, uint64_t sender_op,
+                      const std::string& err);
+  void reject_rndv(Connection* c, uint64_t sender_op, Op* recv,
+                   const std::string& err);
+  // Host bounce -> device recv buffer; the recv completes in poll_gpu.
+  // Fails the op and returns false when the upload cannot start.
+  bool upload_to_recv(Op* r, uint64_t tag, uint64_t len, RawBuf&& bounce);
+  UnexpectedMsg* park_unexpected(Connection* c, uint64_t tag, uint64_t size,
+                                 uint64_t sender_op);
+  bool unpost_recv(Op* r);  // false => r was not posted
+  void forget_send_in_flushes(uint64_t op_id);
+  void fail_flushes_where(const std::function<bool(Op*)>& pred,
+                          const std::string& reason);
+  void complete_drained_flushes();
+  void drop_txq(Connection* c, const std::string& reason);
   void wake();
   Connection* make_listener(const std::string& addr, int port);
 
@@ -533,7 +556,7 @@ class Engine {
   std::deque<std::unique_ptr<UnexpectedMsg>> unexpected_;
   std::vector<Op*> pending_flushes_;
   std::unordered_map<uint64_t, Op*> gpu_sends_;  // op id -> awaiting ack
-  struct GpuPull;  // defined in engine.cpp (holds hipEvent)
+  struct GpuPull;  // engine_internal.hpp (ticket + the recvs it completes)
   std::vector<std::unique_ptr<GpuPull>> gpu_pulls_;
   // Small device pulls collected during a drain, launched batched at the
   // end of the loop iteration (one kernel + one event for up to 8).
@@ -547,6 +570,8 @@ class Engine {
   };
   std::vector<SmallPull> pending_small_pulls_;
   void flush_small_pulls();
+  // Poll `ticket` in poll_gpu; when it lands every item's recv completes.
+  void track_gpu_ticket(void* ticket, std::vector<SmallPull> items);
   // Cross-host GPU send: device->host bounce in flight; when the copy
   // completes the payload goes out as a plain eager frame.
   struct D2hSend {

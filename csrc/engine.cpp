@@ -18,246 +18,11 @@
 //  * close cancels everything still pending with an error containing
 //    "cancel" (reference main.cpp:680-701 contract)
 
-#include "core.hpp"
-#include "shm.hpp"
+#include "engine_internal.hpp"
 
-#include <errno.h>
-#include <fcntl.h>
-#include <ifaddrs.h>
-#include <netinet/in.h>
-#include <netinet/tcp.h>
-#include <poll.h>
-#include <sys/socket.h>
-#include <sys/uio.h>
-#include <sys/syscall.h>
 #include <unistd.h>
 
-#include <chrono>
-#include <cstdio>
-#include <random>
-
 namespace sw {
-
-// ---------------------------------------------------------------------------
-// small utils
-// ---------------------------------------------------------------------------
-
-#ifdef SW_DEBUG
-#define SW_DBG(...)                      \
-  do {                                   \
-    fprintf(stderr, "[sw] " __VA_ARGS__); \
-    fputc('\n', stderr);                 \
-  } while (0)
-#else
-#define SW_DBG(...) \
-  do {              \
-  } while (0)
-#endif
-
-static uint64_t unexp_cap();  // defined with the matching engine below
-
-static void set_nonblocking(int fd) {
-  int fl = fcntl(fd, F_GETFL, 0);
-  fcntl(fd, F_SETFL, fl | O_NONBLOCK);
-}
-
-static void set_tcp_opts(int fd) {
-  int one = 1;
-  setsockopt(fd, IPPROTO_TCP, TCP_NODELAY, &one, sizeof(one));
-  static int buf = (int)env_u64("STARWAY_SOCKBUF", 8 << 20);
-  setsockopt(fd, SOL_SOCKET, SO_SNDBUF, &buf, sizeof(buf));
-  setsockopt(fd, SOL_SOCKET, SO_RCVBUF, &buf, sizeof(buf));
-}
-
-// Stable per-host identifier: FNV-1a over boot_id + hostname, 16 bytes.
-static const uint8_t* host_id() {
-  static uint8_t id[16] = {0};
-  static bool init = [] {
-    std::string seed;
-    FILE* f = fopen("/proc/sys/kernel/random/boot_id", "r");
-    if (f) {
-      char buf[128];
-      size_t n = fread(buf, 1, sizeof(buf), f);
-      seed.append(buf, n);
-      fclose(f);
-    }
-    char hn[256] = {0};
-    gethostname(hn, sizeof(hn) - 1);
-    seed += hn;
-    uint64_t h1 = 1469598103934665603ull, h2 = 14695981039346656037ull;
-    for (unsigned char ch : seed) {
-      h1 = (h1 ^ ch) * 1099511628211ull;
-      h2 = (h2 ^ (ch + 17)) * 1099511628211ull;
-    }
-    memcpy(id, &h1, 8);
-    memcpy(id + 8, &h2, 8);
-    return true;
-  }();
-  (void)init;
-  return id;
-}
-
-const uint8_t* process_uuid() {
-  static uint8_t uuid[16] = {0};
-  static bool init = [] {
-    std::random_device rd;
-    std::mt19937_64 gen(rd() ^ (uint64_t)getpid());
-    for (int i = 0; i < 16; i += 8) {
-      uint64_t v = gen();
-      memcpy(uuid + i, &v, 8);
-    }
-    return true;
-  }();
-  (void)init;
-  return uuid;
-}
-
-std::vector<uint8_t> encode_peer_info(const PeerInfo& pi) {
-  std::vector<uint8_t> out;
-  auto put = [&](const void* p, size_t n) {
-    const uint8_t* b = (const uint8_t*)p;
-    out.insert(out.end(), b, b + n);
-  };
-  uint32_t ver = kProtoVersion;
-  put(&ver, 4);
-  put(&pi.pid, 8);
-  put(pi.uuid, 16);
-  put(pi.host_id, 16);
-  uint8_t hg = pi.has_gpu ? 1 : 0;
-  put(&hg, 1);
-  put(&pi.gpu_count, 4);
-  uint16_t nl = (uint16_t)pi.name.size();
-  put(&nl, 2);
-  put(pi.name.data(), nl);
-  return out;
-}
-
-bool decode_peer_info(const uint8_t* d, size_t len, PeerInfo* out) {
-  if (len < 4 + 8 + 16 + 16 + 1 + 4 + 2) return false;
-  size_t off = 0;
-  uint32_t ver;
-  memcpy(&ver, d + off, 4);
-  off += 4;
-  if (ver != kProtoVersion) return false;
-  memcpy(&out->pid, d + off, 8);
-  off += 8;
-  memcpy(out->uuid, d + off, 16);
-  off += 16;
-  memcpy(out->host_id, d + off, 16);
-  off += 16;
-  out->has_gpu = d[off++] != 0;
-  memcpy(&out->gpu_count, d + off, 4);
-  off += 4;
-  uint16_t nl;
-  memcpy(&nl, d + off, 2);
-  off += 2;
-  if (off + nl > len) return false;
-  out->name.assign((const char*)d + off, nl);
-  return true;
-}
-
-// Worker-address blob:
-//   "SWADDR1\0" | u16 n_addrs | n x { u8 iplen, ip bytes, u16 port } |
-//   u32 peer_len | PeerInfo blob
-static constexpr char kAddrMagic[8] = {'S', 'W', 'A', 'D', 'D', 'R', '1', 0};
-
-static std::vector<std::string> local_ips() {
-  std::vector<std::string> ips;
-  struct ifaddrs* ifs = nullptr;
-  if (getifaddrs(&ifs) == 0) {
-    for (struct ifaddrs* it = ifs; it; it = it->ifa_next) {
-      if (!it->ifa_addr || it->ifa_addr->sa_family != AF_INET) continue;
-      char buf[INET_ADDRSTRLEN];
-      auto* sin = (struct sockaddr_in*)it->ifa_addr;
-      inet_ntop(AF_INET, &sin->sin_addr, buf, sizeof(buf));
-      std::string ip(buf);
-      if (ip == "127.0.0.1")
-        ips.push_back(ip);  // keep, but non-loopback preferred first
-      else
-        ips.insert(ips.begin(), ip);
-    }
-    freeifaddrs(ifs);
-  }
-  if (ips.empty()) ips.push_back("127.0.0.1");
-  return ips;
-}
-
-static std::vector<uint8_t> encode_worker_address(
-    const std::vector<std::pair<std::string, int>>& addrs, const PeerInfo& pi) {
-  std::vector<uint8_t> out(kAddrMagic, kAddrMagic + 8);
-  auto put = [&](const void* p, size_t n) {
-    const uint8_t* b = (const uint8_t*)p;
-    out.insert(out.end(), b, b + n);
-  };
-  uint16_t n = (uint16_t)addrs.size();
-  put(&n, 2);
-  for (auto& [ip, port] : addrs) {
-    uint8_t il = (uint8_t)ip.size();
-    put(&il, 1);
-    put(ip.data(), il);
-    uint16_t p = (uint16_t)port;
-    put(&p, 2);
-  }
-  auto blob = encode_peer_info(pi);
-  uint32_t bl = (uint32_t)blob.size();
-  put(&bl, 4);
-  put(blob.data(), bl);
-  return out;
-}
-
-static bool decode_worker_address(const std::vector<uint8_t>& in,
-                                  std::vector<std::pair<std::string, int>>* addrs,
-                                  PeerInfo* pi) {
-  if (in.size() < 10 || memcmp(in.data(), kAddrMagic, 8) != 0) return false;
-  size_t off = 8;
-  uint16_t n;
-  memcpy(&n, in.data() + off, 2);
-  off += 2;
-  for (int i = 0; i < n; i++) {
-    if (off + 1 > in.size()) return false;
-    uint8_t il = in[off++];
-    if (off + il + 2 > in.size()) return false;
-    std::string ip((const char*)in.data() + off, il);
-    off += il;
-    uint16_t port;
-    memcpy(&port, in.data() + off, 2);
-    off += 2;
-    addrs->emplace_back(ip, port);
-  }
-  if (off + 4 > in.size()) return false;
-  uint32_t bl;
-  memcpy(&bl, in.data() + off, 4);
-  off += 4;
-  if (off + bl > in.size()) return false;
-  return decode_peer_info(in.data() + off, bl, pi);
-}
-
-static PeerInfo self_peer_info(const std::string& name) {
-  PeerInfo pi;
-  pi.pid = (uint64_t)getpid();
-  memcpy(pi.uuid, process_uuid(), 16);
-  memcpy(pi.host_id, host_id(), 16);
-  pi.has_gpu = gpu::available();
-  pi.gpu_count = gpu::device_count();
-  pi.name = name;
-  return pi;
-}
-
-// ---------------------------------------------------------------------------
-// GpuPull — one in-flight GPU delivery (RTS pull or host->device bounce)
-// ---------------------------------------------------------------------------
-
-struct Engine::GpuPull {
-  void* ticket = nullptr;
-  Op* recv_op = nullptr;          // completed with (tag, len) when done
-  Connection* conn = nullptr;     // where to ack
-  uint64_t sender_op_id = 0;      // 0 => no RECV_DONE ack needed (h2d bounce)
-  uint64_t tag = 0;
-  uint64_t len = 0;
-  // Batched small-message pull: completions for every message sharing the
-  // one ticket (recv_op is null in that case).
-  std::vector<Engine::SmallPull> batch;
-};
 
 // ---------------------------------------------------------------------------
 // Engine
@@ -296,37 +61,6 @@ void Engine::wake() {
 }
 
 // ---- Python-thread API ----------------------------------------------------
-
-Connection* Engine::make_listener(const std::string& addr, int port) {
-  int fd = ::socket(AF_INET, SOCK_STREAM | SOCK_CLOEXEC, 0);
-  if (fd < 0) throw std::runtime_error("socket() failed");
-  int one = 1;
-  setsockopt(fd, SOL_SOCKET, SO_REUSEADDR, &one, sizeof(one));
-  struct sockaddr_in sin {};
-  sin.sin_family = AF_INET;
-  sin.sin_port = htons((uint16_t)port);
-  if (inet_pton(AF_INET, addr.c_str(), &sin.sin_addr) != 1) {
-    ::close(fd);
-    throw std::runtime_error("invalid listen address: " + addr);
-  }
-  if (::bind(fd, (struct sockaddr*)&sin, sizeof(sin)) != 0) {
-    ::close(fd);
-    throw std::runtime_error("bind failed on " + addr + ":" +
-                             std::to_string(port) + ": " + strerror(errno));
-  }
-  if (::listen(fd, 128) != 0) {
-    ::close(fd);
-    throw std::runtime_error("listen failed: " + std::string(strerror(errno)));
-  }
-  struct sockaddr_in got {};
-  socklen_t gl = sizeof(got);
-  getsockname(fd, (struct sockaddr*)&got, &gl);
-  listen_port_ = ntohs(got.sin_port);
-  listen_host_ = addr;
-  set_nonblocking(fd);
-  listen_fd_ = fd;
-  return nullptr;
-}
 
 void Engine::listen(const std::string& addr, int port) {
   if (mode_ != ServerMode) throw std::runtime_error("not a server");
@@ -566,137 +300,6 @@ void Engine::thread_main() {
   teardown();
 }
 
-void Engine::do_connect_start() {
-  // Blocking-ish connect with handshake, abortable via status_==3.
-  auto fail = [&](const std::string& why) {
-    Completion comp;
-    comp.kind = Completion::Kind::Connect;
-    comp.error = "not connected: " + why;
-    comp.cb0 = py::object();
-    {
-      py::gil_scoped_acquire gil;
-      try {
-        if (connect_cb_.ptr()) connect_cb_(comp.error);
-      } catch (py::error_already_set& e) {
-        e.discard_as_unraisable("starway connect callback");
-      }
-      connect_cb_ = py::object();
-    }
-    status_.store(4, std::memory_order_release);
-  };
-
-  // Route candidates: worker-address mode may advertise several host IPs;
-  // they are tried round-robin until one connects.
-  if (connect_candidates_.empty())
-    connect_candidates_.emplace_back(connect_host_, connect_port_);
-  size_t cand_idx = 0;
-
-  // Connect with a bounded budget (STARWAY_CONNECT_TIMEOUT seconds,
-  // default 8); ECONNREFUSED is retried within it (the peer may still be
-  // starting up — common in spawn-subprocess tests and rank rendezvous).
-  auto deadline = std::chrono::steady_clock::now() +
-                  std::chrono::seconds(
-                      (long)env_u64("STARWAY_CONNECT_TIMEOUT", 8));
-  int fd = -1;
-  std::string last_err = "connect TIMEOUT";
-  while (fd < 0) {
-    if (status_.load(std::memory_order_acquire) == 3) return fail("canceled");
-    if (std::chrono::steady_clock::now() > deadline) return fail(last_err);
-    auto& [host, port] = connect_candidates_[cand_idx % connect_candidates_.size()];
-    cand_idx++;
-    connect_host_ = host;
-    connect_port_ = port;
-    struct sockaddr_in sin {};
-    sin.sin_family = AF_INET;
-    sin.sin_port = htons((uint16_t)port);
-    if (inet_pton(AF_INET, host.c_str(), &sin.sin_addr) != 1) {
-      last_err = "invalid address " + host;
-      continue;
-    }
-    int s = ::socket(AF_INET, SOCK_STREAM | SOCK_CLOEXEC, 0);
-    if (s < 0) return fail("socket() failed");
-    set_nonblocking(s);
-    set_tcp_opts(s);
-    int r = ::connect(s, (struct sockaddr*)&sin, sizeof(sin));
-    int cerr = 0;
-    if (r == 0) {
-      fd = s;
-      break;
-    }
-    if (errno == EINPROGRESS) {
-      while (true) {
-        if (status_.load(std::memory_order_acquire) == 3) {
-          ::close(s);
-          return fail("canceled");
-        }
-        struct pollfd pfd {s, POLLOUT, 0};
-        int pr = ::poll(&pfd, 1, 20);
-        if (pr > 0) {
-          socklen_t el = sizeof(cerr);
-          getsockopt(s, SOL_SOCKET, SO_ERROR, &cerr, &el);
-          break;
-        }
-        if (std::chrono::steady_clock::now() > deadline) {
-          ::close(s);
-          return fail("connect TIMEOUT");
-        }
-      }
-    } else {
-      cerr = errno;
-    }
-    if (cerr == 0) {
-      fd = s;
-      break;
-    }
-    ::close(s);
-    last_err = std::string("connect: ") + strerror(cerr);
-    if (cerr != ECONNREFUSED && cerr != ENETUNREACH && cerr != EHOSTUNREACH &&
-        cerr != ETIMEDOUT)
-      return fail(last_err);
-    // refused/unreachable: rotate to the next candidate; back off only
-    // once all candidates were tried this round.
-    if (cand_idx % connect_candidates_.size() == 0) usleep(20000);
-  }
-
-  auto c = std::make_unique<Connection>();
-  c->fd = fd;
-  c->conn_id = next_conn_id_++;
-  struct sockaddr_in la {};
-  socklen_t ll = sizeof(la);
-  getsockname(fd, (struct sockaddr*)&la, &ll);
-  char ab[INET_ADDRSTRLEN];
-  inet_ntop(AF_INET, &la.sin_addr, ab, sizeof(ab));
-  c->local_addr = ab;
-  c->local_port = ntohs(la.sin_port);
-  c->remote_addr = connect_host_;
-  c->remote_port = connect_port_;
-  Connection* cp = c.get();
-  conns_.push_back(std::move(c));
-  send_hello(cp);
-
-  // Drive IO until HELLO exchanged (10 s budget).
-  deadline = std::chrono::steady_clock::now() + std::chrono::seconds(10);
-  while (!cp->hello_received) {
-    if (status_.load(std::memory_order_acquire) == 3 || cp->dead) {
-      return fail("canceled or peer reset during handshake");
-    }
-    bool did = false;
-    poll_sockets(5, did);
-    if (std::chrono::steady_clock::now() > deadline)
-      return fail("handshake TIMEOUT");
-  }
-  status_.store(2, std::memory_order_release);
-  {
-    py::gil_scoped_acquire gil;
-    try {
-      if (connect_cb_.ptr()) connect_cb_(std::string(""));
-    } catch (py::error_already_set& e) {
-      e.discard_as_unraisable("starway connect callback");
-    }
-    connect_cb_ = py::object();
-  }
-}
-
 void Engine::loop_iteration(bool& did_work) {
   if (cmd_pending_.load(std::memory_order_acquire)) {
     std::vector<Op*> cmds;
@@ -903,10 +506,7 @@ void Engine::process_command(Op* op) {
       for (Connection* c : targets)
         for (Op* d : c->deferred_sends) op->flush_ops_pending.insert(d->id);
       if (op->flush_write_targets.empty() && op->flush_ops_pending.empty()) {
-        Completion comp;
-        comp.kind = Completion::Kind::FlushDone;
-        comp.op = op;
-        complete(std::move(comp));
+        complete_flush(op);
       } else {
         pending_flushes_.push_back(op);
       }
@@ -971,11 +571,7 @@ void Engine::start_send(Op* op, Connection* c) {
   // FT_SMSG control frame is enqueued HERE so per-connection message order
   // is preserved against eager/RTS traffic. The op completes when the push
   // kernel's event lands (payload captured out of the user buffer).
-  static const bool inbox_tx_on = [] {
-    const char* v = getenv("STARWAY_INBOX");
-    return !(v && !strcmp(v, "0"));
-  }();
-  if (inbox_tx_on && op->buf.device >= 0 && op->buf.rows == 0 &&
+  if (inbox_enabled() && op->buf.device >= 0 && op->buf.rows == 0 &&
       op->buf.size > 0 && !force_xhost && c->inbox_r_active &&
       op->buf.size <= c->inbox_r.slot_bytes - gpu::kInboxHdrBytes &&
       c->inbox_next_seq <= c->inbox_credit_base + c->inbox_r.slots) {
@@ -1030,1889 +626,9 @@ void Engine::start_send(Op* op, Connection* c) {
   } else {
     bool captured = enqueue_eager(c, op);
     on_send_wire_handoff(op, c);  // windowed op: flush id -> write target
-    if (captured) {
-      // Payload written or captured => complete now (eager semantics).
-      Completion comp;
-      comp.kind = Completion::Kind::SendDone;
-      comp.op = op;
-      complete(std::move(comp));
-    }
-    // else: the TxItem owns the op; completion fires at write-out.
-  }
-}
-
-// ---- socket IO ------------------------------------------------------------
-
-void Engine::poll_sockets(int timeout_ms, bool& did_work) {
-  std::vector<struct pollfd> pfds;
-  pfds.push_back({wake_fds_[0], POLLIN, 0});
-  size_t listener_idx = SIZE_MAX;
-  if (listen_fd_ >= 0) {
-    listener_idx = pfds.size();
-    pfds.push_back({listen_fd_, POLLIN, 0});
-  }
-  size_t conn_base = pfds.size();
-  const uint64_t ucap = unexp_cap();
-  std::vector<Connection*> live;
-  for (auto& c : conns_) {
-    if (c->dead || c->fd < 0) continue;
-    // Receive window: over the unexpected-staging cap, stop reading this
-    // connection (socket backpressure) but keep writing our own frames.
-    short ev =
-        (ucap && c->unexp_staged_bytes >= ucap) ? 0 : (short)POLLIN;
-    if (c->want_write()) ev |= POLLOUT;
-    if (!ev) continue;
-    pfds.push_back({c->fd, ev, 0});
-    live.push_back(c.get());
-  }
-  int r = ::poll(pfds.data(), (nfds_t)pfds.size(), timeout_ms);
-  if (r <= 0) return;
-  if (pfds[0].revents & POLLIN) {
-    char buf[256];
-    while (::read(wake_fds_[0], buf, sizeof(buf)) > 0) {
-    }
-  }
-  if (listener_idx != SIZE_MAX && (pfds[listener_idx].revents & POLLIN))
-    accept_new(did_work);
-  for (size_t i = 0; i < live.size(); i++) {
-    short re = pfds[conn_base + i].revents;
-    Connection* c = live[i];
-    if (re & (POLLIN | POLLERR | POLLHUP)) handle_readable(c, did_work);
-    if (!c->dead && (re & POLLOUT)) handle_writable(c, did_work);
-  }
-}
-
-void Engine::accept_new(bool& did_work) {
-  while (true) {
-    struct sockaddr_in ra {};
-    socklen_t rl = sizeof(ra);
-    int fd = ::accept4(listen_fd_, (struct sockaddr*)&ra, &rl, SOCK_CLOEXEC);
-    if (fd < 0) break;
-    set_nonblocking(fd);
-    set_tcp_opts(fd);
-    auto c = std::make_unique<Connection>();
-    c->fd = fd;
-    c->conn_id = next_conn_id_++;
-    char ab[INET_ADDRSTRLEN];
-    inet_ntop(AF_INET, &ra.sin_addr, ab, sizeof(ab));
-    c->remote_addr = ab;
-    c->remote_port = ntohs(ra.sin_port);
-    struct sockaddr_in la {};
-    socklen_t ll = sizeof(la);
-    getsockname(fd, (struct sockaddr*)&la, &ll);
-    inet_ntop(AF_INET, &la.sin_addr, ab, sizeof(ab));
-    c->local_addr = ab;
-    c->local_port = ntohs(la.sin_port);
-    conns_.push_back(std::move(c));
-    // HELLO handshake is responder-style: the server replies only after
-    // registering the endpoint, so by the time the client's connect
-    // completes, list_clients() already shows it (reference contract,
-    // tests/test_basic.py:43-58).
-    did_work = true;
-  }
-}
-
-void Engine::send_hello(Connection* c) {
-  PeerInfo pi = self_peer_info(mode_ == ServerMode ? "server" : "client");
-  auto blob = encode_peer_info(pi);
-  enqueue_frame(c, FT_HELLO, 0, 0, 0, blob.data(), blob.size(),
-                /*priority=*/true);
-  c->hello_sent = true;
-}
-
-void Engine::handle_readable(Connection* c, bool& did_work) {
-  if (c->shm_rx) {
-    // Post-switch the socket carries no frames: drain it only to detect
-    // peer death (EOF/RST). The peer's closing FIN can arrive BEFORE its
-    // remaining ring frames are consumed — defer connection death until
-    // the ring drains (the engine-loop EOF check below finishes the job).
-    char scratch[4096];
-    while (c->fd >= 0) {
-      ssize_t n = ::read(c->fd, scratch, sizeof(scratch));
-      if (n > 0) continue;
-      if (n < 0 && (errno == EAGAIN || errno == EWOULDBLOCK)) return;
-      // EOF or error: stop polling the socket; ring may still hold data.
-      ::close(c->fd);
-      c->fd = -1;
-      c->sock_eof = true;
-      return;
-    }
-    return;
-  }
-  handle_stream(c, /*from_ring=*/false, did_work);
-}
-
-// Shared frame parser over either byte source. The shm handover switches
-// the source exactly at a frame boundary (SHM_ACK / SHM_SWITCH markers),
-// so one parser state machine serves both.
-void Engine::handle_stream(Connection* c, bool from_ring, bool& did_work) {
-  auto src_read = [&](void* dst, size_t want) -> ssize_t {
-    if (from_ring) {
-      size_t n = c->shm->rx.read(dst, want);
-      if (n == 0) return c->shm->rx.peer_closed() ? 0 : -2;
-      return (ssize_t)n;
-    }
-    ssize_t n = ::read(c->fd, dst, want);
-    if (n < 0 && (errno == EAGAIN || errno == EWOULDBLOCK)) return -2;
-    return n;
-  };
-  const uint64_t ucap = unexp_cap();
-  while (!c->dead) {
-    // A mid-stream rx-source switch (SHM_SWITCH parsed from TCP) hands the
-    // remaining frames to the ring reader invoked from the engine loop.
-    if (c->shm_rx != from_ring) return;
-    // Receive window: stop consuming at the next frame boundary once the
-    // unexpected backlog crosses the cap (bounds overshoot to one message;
-    // parser state is preserved and resumes when recvs drain the backlog).
-    if (ucap && c->unexp_staged_bytes >= ucap &&
-        c->rx_state == Connection::RxState::Header && c->rx_got == 0)
-      return;
-    if (c->rx_state == Connection::RxState::Header) {
-      uint8_t* hp = (uint8_t*)&c->rx_hdr;
-      ssize_t n = src_read(hp + c->rx_got, sizeof(FrameHeader) - c->rx_got);
-      if (n == -2) return;
-      if (n <= 0) {
-        on_conn_dead(c);
-        return;
-      }
-      did_work = true;
-      c->rx_got += (size_t)n;
-      if (c->rx_got < sizeof(FrameHeader)) continue;
-      c->rx_got = 0;
-      if (c->rx_hdr.magic != kMagic) {
-        SW_DBG("bad magic from %s:%d", c->remote_addr.c_str(), c->remote_port);
-        on_conn_dead(c);
-        return;
-      }
-      on_frame(c);
-    } else {
-      // Payload streaming.
-      size_t want;
-      uint8_t* dst;
-      if (c->rx_hdr.type == FT_EAGER) {
-        uint64_t done = c->rx_hdr.size - c->rx_msg_remaining;
-        if (c->rx_recv_op && !c->rx_truncated) {
-          // Zero-copy into the posted buffer (or its host bounce for GPU).
-          if (c->rx_recv_op->buf.device >= 0) {
-            dst = c->rx_gpu_bounce.data() + done;
-          } else {
-            dst = c->rx_recv_op->buf.ptr + done;
-          }
-        } else if (c->rx_unexp && !c->rx_discarding) {
-          dst = (c->rx_unexp->redirect_dst ? c->rx_unexp->redirect_dst
-                                           : c->rx_unexp->data.data()) +
-                done;
-        } else {
-          if (c->rx_discard.size() < (64 << 10)) c->rx_discard.resize(64 << 10);
-          dst = c->rx_discard.data();
-        }
-        want = c->rx_msg_remaining;
-        if ((!c->rx_recv_op || c->rx_truncated) && !c->rx_unexp)
-          want = std::min<size_t>(want, c->rx_discard.size());
-      } else {
-        dst = c->rx_small.data() + c->rx_got;
-        want = c->rx_hdr.size - c->rx_got;
-      }
-      ssize_t n = src_read(dst, want);
-      if (n == -2) return;
-      if (n <= 0) {
-        on_conn_dead(c);
-        return;
-      }
-      did_work = true;
-      if (c->rx_hdr.type == FT_EAGER) {
-        c->rx_msg_remaining -= (uint64_t)n;
-        if (c->rx_unexp) c->rx_unexp->got += (uint64_t)n;
-        if (c->rx_msg_remaining == 0) finish_eager_into_recv(c);
-      } else {
-        c->rx_got += (size_t)n;
-        if (c->rx_got == c->rx_hdr.size) {
-          c->rx_got = 0;
-          c->rx_state = Connection::RxState::Header;
-          on_frame_payload(c);
-        }
-      }
-    }
-  }
-}
-
-void Engine::on_frame(Connection* c) {
-  FrameHeader& h = c->rx_hdr;
-  switch (h.type) {
-    case FT_EAGER:
-      begin_eager(c);
-      return;
-    case FT_SMSG:
-      if (h.flags & 1) {
-        // Inbox bring-up probe: verify the seq word actually landed in
-        // our ring (one unpack of zero bytes), then acknowledge with a
-        // CREDIT so the sender activates the plane. Failure = plane
-        // stays off for this connection (fail-closed), loudly.
-        c->inbox_seen_seq = h.op_id;
-        gpu::UnpackMsg um{h.op_id, 0, nullptr};
-        std::string err;
-        void* t =
-            gpu::inbox_unpack(c->inbox_l, &um, 1, engine_lane_, &err);
-        if (t) {
-          auto batch = std::make_unique<UnpackBatch>();
-          batch->ticket = t;
-          batch->conn = c;
-          batch->msgs.push_back(
-              PendingUnpack{c, h.op_id, 0, 0, nullptr, nullptr});
-          batch->done.assign(1, false);
-          batch->remaining = 1;
-          batch->probe = true;
-          unpack_batches_.push_back(std::move(batch));
-        } else {
-          fprintf(stderr, "[starway] inbox probe unpack failed: %s\n",
-                  err.c_str());
-        }
-        return;
-      }
-      handle_smsg(c, h.tag, h.aux, h.op_id);
-      return;
-    case FT_INBOX_CREDIT:
-      if (h.aux > c->inbox_credit_base) c->inbox_credit_base = h.aux;
-      if (!c->inbox_r_active && c->inbox_r.slots &&
-          c->inbox_credit_base >= 1) {
-        // Bring-up probe acknowledged: the push plane is proven live.
-        c->inbox_r_active = true;
-        if (c->ep) c->ep->transports.emplace_back("xgmi", "inbox_push");
-      }
-      return;
-    case FT_HELLO:
-    case FT_RTS:
-    case FT_RTS_CPU:
-    case FT_RECV_FAIL:
-    case FT_SHM_OFFER:
-    case FT_INBOX_OFFER:
-      if (h.size > (16 << 20)) {
-        on_conn_dead(c);
-        return;
-      }
-      c->rx_small.resize(h.size);
-      c->rx_got = 0;
-      c->rx_state = Connection::RxState::Payload;
-      if (h.size == 0) {
-        c->rx_state = Connection::RxState::Header;
-        on_frame_payload(c);
-      }
-      return;
-    case FT_RECV_DONE:
-      on_gpu_send_acked(h.op_id, false, "");
-      return;
-    case FT_FLUSH_REQ:
-      // TCP ordering: by the time we parse this, all earlier bytes on this
-      // stream have been consumed by the engine => safe to ack.
-      enqueue_frame(c, FT_FLUSH_ACK, 0, h.op_id, 0, nullptr, 0, true);
-      return;
-    case FT_FLUSH_ACK:
-      return;  // legacy; flushes complete on write totals
-    case FT_SHM_ACK:
-      // Client accepted (flags 0) or declined (flags 1) the shm channel.
-      // This was the client's LAST tcp frame: subsequent client frames
-      // arrive on the ring.
-      if (h.flags == 0 && c->shm) {
-        enqueue_frame(c, FT_SHM_SWITCH, 0, 0, 0, nullptr, 0, false);
-        c->shm_tx_enq = true;  // frames after SWITCH ride the ring
-        c->shm_rx = true;
-        if (c->ep) c->ep->transports.emplace_back("sm", "shm_ring");
-      } else {
-        c->shm.reset();
-      }
-      return;
-    case FT_SHM_SWITCH:
-      // Server's LAST tcp frame; its later frames arrive on the ring.
-      c->shm_rx = true;
-      return;
-    case FT_BYE:
-      on_conn_dead(c);
-      return;
-    default:
-      on_conn_dead(c);
-      return;
-  }
-}
-
-void Engine::on_frame_payload(Connection* c) {
-  FrameHeader& h = c->rx_hdr;
-  switch (h.type) {
-    case FT_HELLO: {
-      PeerInfo pi;
-      if (!decode_peer_info(c->rx_small.data(), c->rx_small.size(), &pi)) {
-        on_conn_dead(c);
-        return;
-      }
-      c->peer = pi;
-      c->hello_received = true;
-      client_peer_traits_.store(
-          (pi.has_gpu ? 1 : 0) |
-              (memcmp(pi.uuid, process_uuid(), 16) == 0 ? 2 : 0),
-          std::memory_order_release);
-      on_hello(c);
-      break;
-    }
-    case FT_RTS: {
-      if (c->rx_small.size() != sizeof(RtsDesc)) {
-        on_conn_dead(c);
-        return;
-      }
-      RtsDesc rts;
-      memcpy(&rts, c->rx_small.data(), sizeof(rts));
-      handle_rts(c, rts, h.tag, h.aux, h.op_id);
-      break;
-    }
-    case FT_RTS_CPU: {
-      if (c->rx_small.size() != sizeof(CmaDesc)) {
-        on_conn_dead(c);
-        return;
-      }
-      CmaDesc cma;
-      memcpy(&cma, c->rx_small.data(), sizeof(cma));
-      // Match like any other message; unmatched waits in the unexpected
-      // queue as a descriptor.
-      bool matched = false;
-      if (Op* r = take_matching_recv(h.tag)) {
-        start_cma_pull(r, cma, h.tag, h.aux, h.op_id, c);
-        matched = true;
-      }
-      if (!matched) {
-        auto um = std::make_unique<UnexpectedMsg>();
-        um->tag = h.tag;
-        um->size = h.aux;
-        um->conn = c;
-        um->is_cma = true;
-        um->cma = cma;
-        um->sender_op_id = h.op_id;
-        um->complete = true;
-        unexpected_.push_back(std::move(um));
-      }
-      break;
-    }
-    case FT_RECV_FAIL: {
-      std::string err((const char*)c->rx_small.data(), c->rx_small.size());
-      on_gpu_send_acked(h.op_id, true, err);
-      break;
-    }
-    case FT_INBOX_OFFER: {
-      if (c->rx_small.size() != sizeof(gpu::InboxInfo)) break;
-      memcpy(&c->inbox_r, c->rx_small.data(), sizeof(gpu::InboxInfo));
-      if (c->inbox_r.slots && c->inbox_r.slot_bytes > gpu::kInboxHdrBytes &&
-          gpu::available()) {
-        // FAIL-CLOSED bring-up: the ring activates only after a seq-1
-        // probe round-trips (push over xGMI -> peer unpack -> CREDIT).
-        // If the cross-device path misbehaves, the connection simply
-        // keeps using the proven RTS rendezvous plane.
-        c->inbox_r_active = false;
-        c->inbox_next_seq = 2;  // seq 1 is the probe
-        c->inbox_credit_base = 0;
-        bool same_proc = memcmp(c->peer.uuid, process_uuid(), 16) == 0;
-        int run_dev = preferred_device_ >= 0 ? preferred_device_ : 0;
-        gpu::PushMsg probe{nullptr, 0, 1, 0};
-        std::string err;
-        void* ticket = gpu::inbox_push(c->inbox_r, same_proc, run_dev,
-                                       &probe, 1, engine_lane_, &err);
-        if (ticket) {
-          auto batch = std::make_unique<PushBatch>();
-          batch->ticket = ticket;
-          batch->conn = c;  // no ops: progress_pushes just frees it
-          push_batches_.push_back(std::move(batch));
-          enqueue_frame(c, FT_SMSG, 0, 1, 0, nullptr, 0, false,
-                        /*flags=*/1);
-        } else {
-          SW_DBG("inbox probe push failed: %s", err.c_str());
-        }
-      }
-      break;
-    }
-    case FT_SHM_OFFER: {
-      // payload: u64 cap | shm name. Client side: map and ACK (accept) or
-      // decline; the ACK is this side's last tcp frame on accept.
-      bool ok = false;
-      const char* shm_env = getenv("STARWAY_SHM");
-      bool shm_enabled = !(shm_env && (!strcmp(shm_env, "0") ||
-                                       !strcmp(shm_env, "false")));
-      if (c->rx_small.size() > 8 && shm_enabled) {
-        uint64_t cap;
-        memcpy(&cap, c->rx_small.data(), 8);
-        std::string name((const char*)c->rx_small.data() + 8,
-                         c->rx_small.size() - 8);
-        std::string err;
-        ShmChannel* ch = ShmChannel::open(name, cap, &err);
-        if (ch) {
-          c->shm.reset(ch);
-          ok = true;
-        } else {
-          SW_DBG("shm open failed: %s", err.c_str());
-        }
-      }
-      {
-        TxItem ack;
-        FrameHeader ah{};
-        ah.magic = kMagic;
-        ah.type = FT_SHM_ACK;
-        ah.flags = ok ? 0 : 1;
-        ack.head.resize(sizeof(ah));
-        memcpy(ack.head.data(), &ah, sizeof(ah));
-        c->tx_enqueued_bytes += ack.head.size();
-        c->txq.push_back(std::move(ack));  // tcp (enqueued pre-switch)
-      }
-      if (ok) c->shm_tx_enq = true;  // everything after the ACK rides the ring
-      bool dummy = false;
-      handle_writable(c, dummy);
-      break;
-    }
-    default:
-      break;
-  }
-}
-
-void Engine::on_hello(Connection* c) {
-  if (mode_ == ServerMode) {
-    auto ep = std::make_shared<EndpointInfo>();
-    ep->name = "ep-" + std::to_string(c->conn_id) + "@" + c->remote_addr + ":" +
-               std::to_string(c->remote_port);
-    ep->local_addr = c->local_addr;
-    ep->local_port = c->local_port;
-    ep->remote_addr = c->remote_addr;
-    ep->remote_port = c->remote_port;
-    ep->conn = c;
-    ep->owner = this;
-    ep->peer_has_gpu = c->peer.has_gpu;
-    ep->peer_same_proc = memcmp(c->peer.uuid, process_uuid(), 16) == 0;
-    ep->transports.emplace_back("tcp", "sock");
-    if (gpu::available() && c->peer.has_gpu) {
-      bool same_proc = memcmp(c->peer.uuid, process_uuid(), 16) == 0;
-      ep->transports.emplace_back("xgmi", same_proc ? "p2p" : "hipipc");
-      ep->transports.emplace_back("hbm", "gfx950_copy");
-    }
-    c->ep = ep;
-    {
-      std::lock_guard<std::mutex> lk(ep_mu_);
-      eps_.push_back(ep);
-    }
-    send_hello(c);  // responder reply; unblocks the client's connect
-    // Same-host peer: offer the shared-memory ring channel (disable with
-    // STARWAY_SHM=0 — any value set disables; unset enables).
-    const char* shm_env = getenv("STARWAY_SHM");
-    bool shm_enabled = !(shm_env && (!strcmp(shm_env, "0") ||
-                                     !strcmp(shm_env, "false")));
-    if (memcmp(c->peer.host_id, host_id(), 16) == 0 && shm_enabled) {
-      static std::atomic<uint64_t> shm_seq{1};
-      uint64_t cap = env_u64("STARWAY_SHM_RING", 8 << 20);
-      // round up to a power of two (ring indexing masks with cap-1)
-      uint64_t p2 = 4096;
-      while (p2 < cap) p2 <<= 1;
-      cap = p2;
-      char name[96];
-      snprintf(name, sizeof(name), "/sw-%d-%llu-%llu", (int)getpid(),
-               (unsigned long long)c->conn_id,
-               (unsigned long long)shm_seq.fetch_add(1));
-      std::string err;
-      ShmChannel* ch = ShmChannel::create(name, cap, &err);
-      if (ch) {
-        c->shm.reset(ch);
-        std::vector<uint8_t> payload(8 + strlen(name));
-        memcpy(payload.data(), &cap, 8);
-        memcpy(payload.data() + 8, name, strlen(name));
-        enqueue_frame(c, FT_SHM_OFFER, 0, 0, 0, payload.data(),
-                      payload.size(), false);
-      } else {
-        SW_DBG("shm create failed: %s", err.c_str());
-      }
-    }
-    if (have_accept_cb_) {
-      Completion comp;
-      comp.kind = Completion::Kind::Accept;
-      comp.ep = ep;
-      complete(std::move(comp));
-    }
-  }
-  // Small-message inbox: both sides offer their ring to any same-host GPU
-  // peer (including same-process loopback, which uses the raw pointer).
-  // STARWAY_INBOX=0 disables.
-  static const bool inbox_on = [] {
-    const char* v = getenv("STARWAY_INBOX");
-    return !(v && !strcmp(v, "0"));
-  }();
-  if (inbox_on && gpu::available() && c->peer.has_gpu &&
-      memcmp(c->peer.host_id, host_id(), 16) == 0 && !c->inbox_l_active) {
-    std::string err;
-    if (gpu::inbox_create(&c->inbox_l, preferred_device_, &err)) {
-      c->inbox_l_active = true;
-      enqueue_frame(c, FT_INBOX_OFFER, 0, 0, 0, &c->inbox_l,
-                    sizeof(gpu::InboxInfo), false);
-    } else {
-      SW_DBG("inbox create failed: %s", err.c_str());
-    }
-  }
-}
-
-// ---- eager path -----------------------------------------------------------
-
-void Engine::begin_eager(Connection* c) {
-  uint64_t msg_len = c->rx_hdr.size;
-  uint64_t tag = c->rx_hdr.tag;
-  c->rx_recv_op = nullptr;
-  c->rx_unexp = nullptr;
-  c->rx_truncated = false;
-  c->rx_discarding = false;
-  c->rx_msg_remaining = msg_len;
-
-  // Match against posted recvs in FIFO order.
-  if (Op* r = take_matching_recv(tag)) {
-    {
-      if (msg_len > r->buf.size ||
-          (r->buf.rows > 0 && msg_len != r->buf.size)) {
-        // Truncation / strided-geometry mismatch: consume + fail
-        // (UCX MESSAGE_TRUNCATED analog; a strided window needs the exact
-        // message size or partial rows would smear).
-        c->rx_truncated = true;
-        c->rx_recv_op = r;
-      } else {
-        c->rx_recv_op = r;
-        if (r->buf.device >= 0 && !c->rx_gpu_bounce.alloc(msg_len)) {
-          // Cannot stage the host bounce: fail the recv, then consume and
-          // discard the stream bytes (truncation machinery reused with the
-          // op already failed).
-          c->rx_recv_op = nullptr;
-          fail_op(r, "receive failed: host bounce allocation failed");
-          c->rx_state =
-              msg_len ? Connection::RxState::Payload : Connection::RxState::Header;
-          c->rx_discarding = true;
-          return;
-        }
-      }
-      c->rx_recv_op->recv_sender_tag = tag;
-      c->rx_recv_op->recv_len = msg_len;
-    }
-  }
-  if (!c->rx_recv_op) {
-    stats_.unexpected_rx.fetch_add(1, std::memory_order_relaxed);
-    auto um = std::make_unique<UnexpectedMsg>();
-    um->tag = tag;
-    um->size = msg_len;
-    um->conn = c;
-    if (!um->data.alloc(msg_len)) {
-      // Cannot stage it: drop the connection rather than the process.
-      SW_DBG("unexpected staging alloc failed (%llu bytes)",
-             (unsigned long long)msg_len);
-      on_conn_dead(c);
-      return;
-    }
-    // Flow control: staged bytes count against the connection's receive
-    // window; past STARWAY_UNEXP_CAP the engine stops reading this
-    // connection until recvs drain the backlog (TCP/ring backpressure
-    // reaches the sender instead of unbounded staging growth).
-    um->staged = msg_len;
-    c->unexp_staged_bytes += msg_len;
-    stats_.unexp_staged_bytes.fetch_add(msg_len, std::memory_order_relaxed);
-    c->rx_unexp = um.get();
-    unexpected_.push_back(std::move(um));
-  }
-  if (msg_len == 0) {
-    finish_eager_into_recv(c);
-  } else {
-    c->rx_state = Connection::RxState::Payload;
-  }
-}
-
-void Engine::finish_eager_into_recv(Connection* c) {
-  c->rx_state = Connection::RxState::Header;
-  c->rx_got = 0;
-  if (c->rx_discarding) {
-    c->rx_discarding = false;
-    return;
-  }
-  if (c->rx_recv_op) {
-    Op* r = c->rx_recv_op;
-    c->rx_recv_op = nullptr;
-    if (c->rx_truncated) {
-      c->rx_truncated = false;
-      fail_op(r, "receive failed: message truncated (len " +
-                     std::to_string(r->recv_len) + " > buffer " +
-                     std::to_string(r->buf.size) + ")");
-      return;
-    }
-    if (r->buf.device >= 0) {
-      // Host->device bounce upload.
-      std::string err;
-      void* ticket = gpu::begin_h2d(r->buf, c->rx_gpu_bounce.data(),
-                                    r->recv_len, &err);
-      if (!ticket) {
-        fail_op(r, "receive failed: " + err);
-        return;
-      }
-      auto pull = std::make_unique<GpuPull>();
-      pull->ticket = ticket;
-      pull->recv_op = r;
-      pull->conn = c;
-      pull->sender_op_id = 0;
-      pull->tag = r->recv_sender_tag;
-      pull->len = r->recv_len;
-      gpu::attach_bounce(ticket, std::move(c->rx_gpu_bounce));
-      c->rx_gpu_bounce.clear();
-      gpu_pulls_.push_back(std::move(pull));
-      return;
-    }
-    stats_.msgs_received.fetch_add(1, std::memory_order_relaxed);
-    stats_.bytes_received.fetch_add(r->recv_len, std::memory_order_relaxed);
-    stats_.eager_rx.fetch_add(1, std::memory_order_relaxed);
-    Completion comp;
-    comp.kind = Completion::Kind::RecvDone;
-    comp.op = r;
-    comp.a = r->recv_sender_tag;
-    comp.b = r->recv_len;
-    complete(std::move(comp));
-  } else if (c->rx_unexp) {
-    c->rx_unexp->complete = true;
-    UnexpectedMsg* um = c->rx_unexp;
-    c->rx_unexp = nullptr;
-    if (um->bound_recv) {
-      Op* r = um->bound_recv;
-      um->bound_recv = nullptr;
-      // Transfer ownership out of the unexpected queue before delivering.
-      for (auto it = unexpected_.begin(); it != unexpected_.end(); ++it) {
-        if (it->get() == um) {
-          it->release();
-          unexpected_.erase(it);
-          break;
-        }
-      }
-      complete_recv_from_unexpected(r, um);
-    }
-  }
-}
-
-// ---- GPU rendezvous -------------------------------------------------------
-
-void Engine::handle_rts(Connection* c, const RtsDesc& rts, uint64_t tag,
-                        uint64_t size, uint64_t sender_op) {
-  if (Op* r = take_matching_recv(tag)) {
-    start_gpu_pull(r, rts, tag, size, sender_op, c);
-    return;
-  }
-  auto um = std::make_unique<UnexpectedMsg>();
-  um->tag = tag;
-  um->size = size;
-  um->conn = c;
-  um->is_rts = true;
-  um->rts = rts;
-  um->sender_op_id = sender_op;
-  um->complete = true;
-  unexpected_.push_back(std::move(um));
-}
-
-void Engine::start_gpu_pull(Op* recv_op, const RtsDesc& rts, uint64_t tag,
-                            uint64_t size, uint64_t sender_op, Connection* c) {
-  if (size > recv_op->buf.size) {
-    std::string err = "message truncated (len " + std::to_string(size) +
-                      " > buffer " + std::to_string(recv_op->buf.size) + ")";
-    enqueue_frame(c, FT_RECV_FAIL, 0, sender_op, 0, err.data(), err.size(),
-                  true);
-    fail_op(recv_op, "receive failed: " + err);
-    return;
-  }
-  // Small contiguous device->device messages are batched: collected here,
-  // launched as one multi-copy kernel + one event at the end of the loop
-  // iteration (the per-launch cost dominates small-message rate).
-  static const uint64_t kMultiMax = env_u64("STARWAY_MULTI_COPY_MAX", 65536);
-  if (size > 0 && size <= kMultiMax && recv_op->buf.device >= 0 &&
-      recv_op->buf.rows == 0 && rts.src_rows == 0) {
-    pending_small_pulls_.push_back(
-        SmallPull{rts, recv_op, c, sender_op, tag, size});
-    return;
-  }
-  std::string err;
-  void* ticket = gpu::begin_pull(rts, recv_op->buf, size, &err);
-  if (!ticket) {
-    enqueue_frame(c, FT_RECV_FAIL, 0, sender_op, 0, err.data(), err.size(),
-                  true);
-    fail_op(recv_op, "receive failed: " + err);
-    return;
-  }
-  auto pull = std::make_unique<GpuPull>();
-  pull->ticket = ticket;
-  pull->recv_op = recv_op;
-  pull->conn = c;
-  pull->sender_op_id = sender_op;
-  pull->tag = tag;
-  pull->len = size;
-  gpu_pulls_.push_back(std::move(pull));
-}
-
-void Engine::flush_small_pulls() {
-  // Group by destination device; launch batches of up to 8 per kernel. A
-  // lone pull goes through the ordinary single path.
-  while (!pending_small_pulls_.empty()) {
-    int dev = pending_small_pulls_[0].recv_op->buf.device;
-    gpu::PullReq reqs[8];
-    SmallPull items[8];
-    int n = 0;
-    for (size_t i = 0; i < pending_small_pulls_.size() && n < 8;) {
-      if (pending_small_pulls_[i].recv_op->buf.device == dev) {
-        items[n] = pending_small_pulls_[i];
-        reqs[n] = gpu::PullReq{items[n].rts, items[n].recv_op->buf.ptr, dev,
-                               items[n].size};
-        n++;
-        pending_small_pulls_.erase(pending_small_pulls_.begin() + i);
-      } else {
-        i++;
-      }
-    }
-    std::string err;
-    void* ticket = nullptr;
-    if (n == 1) {
-      ticket = gpu::begin_pull(items[0].rts, items[0].recv_op->buf,
-                               items[0].size, &err);
-    } else {
-      ticket = gpu::begin_pull_multi(reqs, n, &err);
-    }
-    if (!ticket) {
-      for (int i = 0; i < n; i++) {
-        if (items[i].conn && !items[i].conn->dead)
-          enqueue_frame(items[i].conn, FT_RECV_FAIL, 0,
-                        items[i].sender_op_id, 0, err.data(), err.size(),
-                        true);
-        fail_op(items[i].recv_op, "receive failed: " + err);
-      }
-      continue;
-    }
-    auto pull = std::make_unique<GpuPull>();
-    pull->ticket = ticket;
-    if (n == 1) {
-      pull->recv_op = items[0].recv_op;
-      pull->conn = items[0].conn;
-      pull->sender_op_id = items[0].sender_op_id;
-      pull->tag = items[0].tag;
-      pull->len = items[0].size;
-    } else {
-      pull->batch.assign(items, items + n);
-    }
-    gpu_pulls_.push_back(std::move(pull));
-  }
-}
-
-// ---- small-message inbox plane --------------------------------------------
-
-void Engine::inbox_release_seq(Connection* c, uint64_t seq) {
-  c->inbox_released.insert(seq);
-  while (c->inbox_released.count(c->inbox_consumed + 1)) {
-    c->inbox_released.erase(c->inbox_consumed + 1);
-    c->inbox_consumed++;
-  }
-  if (!c->dead &&
-      c->inbox_consumed - c->inbox_credited >=
-          std::max<uint64_t>(1, c->inbox_l.slots / 4)) {
-    enqueue_frame(c, FT_INBOX_CREDIT, 0, 0, c->inbox_consumed, nullptr, 0,
-                  true);
-    c->inbox_credited = c->inbox_consumed;
-  }
-}
-
-// Route one announced inbox message to a matched recv: batched local
-// unpack kernel (device dst) or pinned bounce (host / strided dst).
-void Engine::dispatch_smsg_to_recv(Connection* c, Op* r, uint64_t tag,
-                                   uint64_t size, uint64_t seq) {
-  if (size > r->buf.size || (r->buf.rows > 0 && size != r->buf.size)) {
-    fail_op(r, "receive failed: message truncated (len " +
-                   std::to_string(size) + " > buffer " +
-                   std::to_string(r->buf.size) + ")");
-    inbox_release_seq(c, seq);  // discard without reading the slot
-    return;
-  }
-  uint8_t* dst = nullptr;
-  if (r->buf.device >= 0 && r->buf.rows == 0 &&
-      r->buf.device == c->inbox_l.device)
-    dst = r->buf.ptr;
-  pending_unpacks_.push_back(PendingUnpack{c, seq, size, tag, r, dst});
-}
-
-void Engine::handle_smsg(Connection* c, uint64_t tag, uint64_t size,
-                         uint64_t seq) {
-  c->inbox_seen_seq = seq;
-  arm_streak_ = 0;
-  arm_backoff_ = false;
-  // Doorbell copy that raced a disarm: this frame carries its tag.
-  if (armed_done_.active && armed_done_.conn == c && armed_done_.seq == seq) {
-    Op* r = armed_done_.recv_op;
-    armed_done_ = ArmedDone{};
-    stats_.msgs_received.fetch_add(1, std::memory_order_relaxed);
-    stats_.bytes_received.fetch_add(size, std::memory_order_relaxed);
-    stats_.inbox_rx.fetch_add(1, std::memory_order_relaxed);
-    stats_.doorbell_rx.fetch_add(1, std::memory_order_relaxed);
-    Completion comp;
-    comp.kind = Completion::Kind::RecvDone;
-    comp.op = r;
-    comp.a = tag;
-    comp.b = size;
-    complete(std::move(comp));
-    inbox_release_seq(c, seq);
-    try_arm();
-    return;
-  }
-  // Doorbell fast path: a pre-armed kernel is watching exactly this seq.
-  if (armed_.ticket && armed_.conn == c && armed_.seq == seq) {
-    static const bool dbg_arm2 = getenv("STARWAY_DEBUG_ARM") != nullptr;
-    auto dbg_t0 = std::chrono::steady_clock::now();
-    uint64_t sz = 0;
-    int st = gpu::arm_poll(armed_.ticket, &sz);
-    int st_first = st;
-    if (st == 0) {
-      // The payload and this control frame race each other; the kernel
-      // sees the slot within microseconds of the xGMI write landing.
-      auto deadline = std::chrono::steady_clock::now() +
-                      std::chrono::milliseconds(
-                          (long)env_u64("STARWAY_ARM_WAIT_MS", 2));
-      while ((st = gpu::arm_poll(armed_.ticket, &sz)) == 0) {
-        if (std::chrono::steady_clock::now() > deadline) break;
-      }
-      if (st == 0) {
-        gpu::arm_cancel(armed_.ticket);
-        auto hard = std::chrono::steady_clock::now() +
-                    std::chrono::milliseconds(100);
-        while ((st = gpu::arm_poll(armed_.ticket, &sz)) == 0 &&
-               std::chrono::steady_clock::now() < hard)
-          sched_yield();
-        // Diagnostic (STARWAY_DEBUG_ARM=1): a doorbell that had to be
-        // canceled because it never reported, with its final state.
-        static const bool dbg_arm = getenv("STARWAY_DEBUG_ARM") != nullptr;
-        if (dbg_arm)
-          fprintf(stderr, "[sw-arm] seq=%llu missed, final st=%d\n",
-                  (unsigned long long)seq, st);
-      }
-    }
-    if (dbg_arm2) {
-      double us = std::chrono::duration<double, std::micro>(
-                      std::chrono::steady_clock::now() - dbg_t0)
-                      .count();
-      if (us > 100 || st != 1)
-        fprintf(stderr,
-                "[sw-arm] seq=%llu first_st=%d final_st=%d wait=%.0fus\n",
-                (unsigned long long)seq, st_first, st, us);
-    }
-    Op* r = armed_.recv_op;
-    retire_armed_ticket(armed_.ticket);
-    armed_ = Armed{};
-    if (st == 1) {
-      for (auto it = posted_recvs_.begin(); it != posted_recvs_.end(); ++it)
-        if (*it == r) {
-          posted_recvs_.erase(it);
-          break;
-        }
-      stats_.msgs_received.fetch_add(1, std::memory_order_relaxed);
-      stats_.bytes_received.fetch_add(sz, std::memory_order_relaxed);
-      stats_.inbox_rx.fetch_add(1, std::memory_order_relaxed);
-      stats_.doorbell_rx.fetch_add(1, std::memory_order_relaxed);
-      Completion comp;
-      comp.kind = Completion::Kind::RecvDone;
-      comp.op = r;
-      comp.a = tag;
-      comp.b = sz;
-      complete(std::move(comp));
-      inbox_release_seq(c, seq);
-      try_arm();
-      return;
-    }
-    // nomatch / canceled / expired / stuck: the recv stays posted and the
-    // message goes through the ordinary path below.
-  }
-  if (Op* r = take_matching_recv(tag)) {
-    dispatch_smsg_to_recv(c, r, tag, size, seq);
-    return;
-  }
-  stats_.unexpected_rx.fetch_add(1, std::memory_order_relaxed);
-  auto um = std::make_unique<UnexpectedMsg>();
-  um->tag = tag;
-  um->size = size;
-  um->conn = c;
-  um->is_smsg = true;
-  um->smsg_seq = seq;
-  um->complete = true;
-  unexpected_.push_back(std::move(um));
-}
-
-void Engine::flush_pending_pushes() {
-  for (auto& [c, vec] : pending_pushes_) {
-    if (vec.empty()) continue;
-    if (c->dead) {
-      for (auto& pp : vec) {
-        gpu_sends_.erase(pp.op->id);
-        fail_op(pp.op, "send failed: connection reset");
-      }
-      vec.clear();
-      continue;
-    }
-    bool same_proc = memcmp(c->peer.uuid, process_uuid(), 16) == 0;
-    size_t i = 0;
-    while (i < vec.size()) {
-      // One launch per (destination ring, source device) batch.
-      int run_dev = vec[i].op->buf.device;
-      gpu::PushMsg msgs[32];
-      auto batch = std::make_unique<PushBatch>();
-      batch->conn = c;
-      int n = 0;
-      size_t j = i;
-      while (j < vec.size() && n < 32) {
-        if (vec[j].op->buf.device != run_dev) {
-          j++;
-          continue;
-        }
-        msgs[n] = gpu::PushMsg{vec[j].op->buf.ptr,
-                               (uint32_t)vec[j].op->buf.size, vec[j].seq,
-                               vec[j].op->tag};
-        batch->ops.push_back(vec[j].op);
-        vec.erase(vec.begin() + j);
-        n++;
-      }
-      std::string err;
-      batch->ticket =
-          gpu::inbox_push(c->inbox_r, same_proc, run_dev, msgs, n,
-                          engine_lane_, &err);
-      if (!batch->ticket) {
-        // Push plane broken: fail these sends and stop using the inbox.
-        c->inbox_r_active = false;
-        for (Op* op : batch->ops) {
-          gpu_sends_.erase(op->id);
-          fail_op(op, "send failed: " + err);
-        }
-      } else {
-        push_batches_.push_back(std::move(batch));
-      }
-    }
-  }
-  pending_pushes_.clear();
-}
-
-void Engine::progress_pushes(bool& did_work) {
-  for (size_t i = 0; i < push_batches_.size();) {
-    PushBatch* b = push_batches_[i].get();
-    std::string err;
-    int r = gpu::push_poll(b->ticket, &err);
-    if (r == 0) {
-      i++;
-      continue;
-    }
-    did_work = true;
-    gpu::push_free(b->ticket);
-    for (Op* op : b->ops) {
-      gpu_sends_.erase(op->id);
-      if (r < 0) {
-        for (Op* f : pending_flushes_) f->flush_ops_pending.erase(op->id);
-        fail_op(op, "send failed: " + err);
-      } else if (!b->conn || b->conn->dead) {
-        for (Op* f : pending_flushes_) f->flush_ops_pending.erase(op->id);
-        fail_op(op, "send failed: connection reset");
-      } else {
-        on_send_wire_handoff(op, b->conn);
-        Completion comp;
-        comp.kind = Completion::Kind::SendDone;
-        comp.op = op;
-        complete(std::move(comp));
-      }
-    }
-    push_batches_.erase(push_batches_.begin() + i);
-  }
-}
-
-void Engine::flush_pending_unpacks() {
-  while (!pending_unpacks_.empty()) {
-    Connection* c = pending_unpacks_[0].conn;
-    auto batch = std::make_unique<UnpackBatch>();
-    batch->conn = c;
-    gpu::UnpackMsg msgs[32];
-    int n = 0;
-    for (size_t i = 0; i < pending_unpacks_.size() && n < 32;) {
-      if (pending_unpacks_[i].conn == c) {
-        msgs[n] = gpu::UnpackMsg{pending_unpacks_[i].seq,
-                                 (uint32_t)pending_unpacks_[i].size,
-                                 pending_unpacks_[i].dst};
-        batch->msgs.push_back(pending_unpacks_[i]);
-        pending_unpacks_.erase(pending_unpacks_.begin() + i);
-        n++;
-      } else {
-        i++;
-      }
-    }
-    std::string err;
-    batch->ticket =
-        gpu::inbox_unpack(c->inbox_l, msgs, n, engine_lane_, &err);
-    if (!batch->ticket) {
-      for (auto& m : batch->msgs) {
-        fail_op(m.recv_op, "receive failed: " + err);
-        inbox_release_seq(c, m.seq);
-      }
-      continue;
-    }
-    batch->done.assign(batch->msgs.size(), false);
-    batch->remaining = batch->msgs.size();
-    unpack_batches_.push_back(std::move(batch));
-  }
-}
-
-void Engine::progress_unpacks(bool& did_work) {
-  for (size_t i = 0; i < unpack_batches_.size();) {
-    UnpackBatch* b = unpack_batches_[i].get();
-    for (size_t k = 0; k < b->msgs.size(); k++) {
-      if (b->done[k]) continue;
-      std::string err;
-      int r = gpu::unpack_poll(b->ticket, (int)k, &err);
-      if (r == 0) continue;
-      did_work = true;
-      b->done[k] = true;
-      b->remaining--;
-      PendingUnpack& m = b->msgs[k];
-      if (b->probe) {
-        if (r > 0 && m.conn && !m.conn->dead) {
-          m.conn->inbox_consumed = m.seq;
-          m.conn->inbox_credited = m.seq;
-          enqueue_frame(m.conn, FT_INBOX_CREDIT, 0, 0, m.seq, nullptr, 0,
-                        true);
-        } else if (r < 0) {
-          fprintf(stderr,
-                  "[starway] inbox bring-up probe never landed — push "
-                  "plane disabled for this connection (RTS fallback)\n");
-        }
-        continue;
-      }
-      if (r < 0) {
-        // The in-kernel wait expired before the payload landed. Under a
-        // loaded launch queue the push kernel can start tens of ms late,
-        // so retry (fresh unpack kernel) before declaring the message
-        // lost (sender died mid-push => recv stays pending, the
-        // unflushed-close contract).
-        if (m.retries + 1 < 50 && m.conn && !m.conn->dead) {
-          PendingUnpack again = m;
-          again.retries++;
-          pending_unpacks_.push_back(again);
-        } else {
-          repost_recv_front(m.recv_op);
-          inbox_release_seq(m.conn, m.seq);
-        }
-        continue;
-      }
-      if (!m.dst) {
-        const uint8_t* bounce = gpu::unpack_bounce(b->ticket, (int)k);
-        if (m.recv_op->buf.device < 0) {
-          memcpy(m.recv_op->buf.ptr, bounce, m.size);
-        } else {
-          // Strided / other-device recv: re-upload from a heap copy via
-          // the ordinary h2d machinery (rare path, <= slot capacity).
-          RawBuf heap;
-          std::string err2;
-          if (!heap.alloc(m.size)) {
-            fail_op(m.recv_op, "receive failed: bounce allocation failed");
-            inbox_release_seq(m.conn, m.seq);
-            continue;
-          }
-          memcpy(heap.data(), bounce, m.size);
-          void* ticket =
-              gpu::begin_h2d(m.recv_op->buf, heap.data(), m.size, &err2);
-          if (!ticket) {
-            fail_op(m.recv_op, "receive failed: " + err2);
-            inbox_release_seq(m.conn, m.seq);
-            continue;
-          }
-          auto pull = std::make_unique<GpuPull>();
-          pull->ticket = ticket;
-          pull->recv_op = m.recv_op;
-          pull->conn = nullptr;
-          pull->sender_op_id = 0;
-          pull->tag = m.tag;
-          pull->len = m.size;
-          gpu::attach_bounce(ticket, std::move(heap));
-          gpu_pulls_.push_back(std::move(pull));
-          inbox_release_seq(m.conn, m.seq);
-          continue;
-        }
-      }
-      stats_.msgs_received.fetch_add(1, std::memory_order_relaxed);
-      stats_.bytes_received.fetch_add(m.size, std::memory_order_relaxed);
-      stats_.inbox_rx.fetch_add(1, std::memory_order_relaxed);
-      Completion comp;
-      comp.kind = Completion::Kind::RecvDone;
-      comp.op = m.recv_op;
-      comp.a = m.tag;
-      comp.b = m.size;
-      complete(std::move(comp));
-      inbox_release_seq(m.conn, m.seq);
-    }
-    if (b->remaining == 0) {
-      gpu::unpack_free(b->ticket);
-      unpack_batches_.erase(unpack_batches_.begin() + i);
-    } else {
-      i++;
-    }
-  }
-}
-
-void Engine::try_arm() {
-  // Opt-in (STARWAY_DOORBELL=1): measured on MI355X the pre-armed
-  // doorbell wins ~1.4 us one-way on a pre-posted recv but costs ~5 us
-  // per direction in bidirectional pingpong (per-message arm launches on
-  // both engines), so the batched-unpack path is the default.
-  static const bool arm_on = [] {
-    const char* v = getenv("STARWAY_DOORBELL");
-    return v && !strcmp(v, "1");
-  }();
-  if (!arm_on || armed_.ticket || armed_done_.active || arm_backoff_)
-    return;
-  // Latency pattern only: with several recvs outstanding (throughput
-  // pattern) a doorbell would serialize the batched unpack path into one
-  // arm launch + inline wait per message.
-  if (posted_recvs_.size() != 1) return;
-  Op* r = posted_recvs_.front();
-  if (r->buf.device < 0 || r->buf.rows > 0 || r->buf.size == 0) return;
-  // Only safe with exactly one live connection (its inbox FIFO is then the
-  // only source of inbox messages that could race the doorbell).
-  Connection* target = nullptr;
-  int n_live = 0;
-  for (auto& c : conns_) {
-    if (c->dead) continue;
-    n_live++;
-    target = c.get();
-  }
-  if (n_live != 1 || !target || !target->inbox_l_active) return;
-  if (r->buf.device != target->inbox_l.device) return;
-  // Only worth a resident kernel when the expected message can actually
-  // ride the inbox (small buffer): large recvs are served by the RTS pull
-  // path and would just churn expired doorbells.
-  if (r->buf.size > target->inbox_l.slot_bytes - gpu::kInboxHdrBytes) return;
-  // Never skip ahead of inbox messages already being delivered.
-  if (!pending_unpacks_.empty() || !unpack_batches_.empty()) return;
-  for (auto& um : unexpected_)
-    if (um->is_smsg && um->conn == target) return;
-  std::string err;
-  void* t = gpu::arm_recv(target->inbox_l, target->inbox_seen_seq + 1,
-                          r->tag, r->tag_mask, r->buf.ptr, r->buf.size,
-                          engine_lane_, &err);
-  if (!t) {
-    SW_DBG("arm failed: %s", err.c_str());
-    return;
-  }
-  armed_ = Armed{t, r, target, target->inbox_seen_seq + 1};
-}
-
-void Engine::progress_armed(bool& did_work) {
-  if (!armed_.ticket) return;
-  uint64_t sz = 0;
-  int st = gpu::arm_poll(armed_.ticket, &sz);
-  if (st == 4) {
-    // Bounded wait expired with no message: re-arm at the same sequence,
-    // but only a few times in a row — continuous re-arming keeps a
-    // spinning kernel resident ~100% of the time, which starves streams
-    // sharing its hardware queue. After the streak the doorbell stands
-    // down until traffic resumes (handle_smsg) or a recv is posted.
-    did_work = true;
-    gpu::arm_free(armed_.ticket);
-    armed_ = Armed{};
-    if (++arm_streak_ >= 3) {
-      arm_backoff_ = true;
-      return;
-    }
-    try_arm();
-  }
-  // 1 (copied) / 2 (nomatch) are resolved by handle_smsg when the control
-  // frame lands; 0 keeps waiting.
-}
-
-void Engine::start_cma_pull(Op* recv_op, const CmaDesc& cma, uint64_t tag,
-                            uint64_t size, uint64_t sender_op,
-                            Connection* c) {
-  if (size > recv_op->buf.size ||
-      (recv_op->buf.rows > 0 && size != recv_op->buf.size)) {
-    std::string err = "message truncated (len " + std::to_string(size) +
-                      " > buffer " + std::to_string(recv_op->buf.size) + ")";
-    enqueue_frame(c, FT_RECV_FAIL, 0, sender_op, 0, err.data(), err.size(),
-                  true);
-    fail_op(recv_op, "receive failed: " + err);
-    return;
-  }
-  auto pull = std::make_unique<CmaPull>();
-  if (recv_op->buf.device >= 0) {
-    // The posted recv buffer lives on a GPU: process_vm_readv cannot write
-    // device memory, so pull into a host bounce and upload with begin_h2d
-    // at completion. If the bounce cannot be allocated, decline CMA — the
-    // sender retransmits as eager, which handles device recvs natively.
-    if (!pull->bounce.alloc(size)) {
-      std::string err = "cma unavailable (bounce allocation failed)";
-      enqueue_frame(c, FT_RECV_FAIL, 0, sender_op, 0, err.data(), err.size(),
-                    true);
-      repost_recv_front(recv_op);
-      return;
-    }
-  }
-  pull->recv_op = recv_op;
-  pull->conn = c;
-  pull->sender_op_id = sender_op;
-  pull->tag = tag;
-  pull->size = size;
-  pull->desc = cma;
-  cma_pulls_.push_back(std::move(pull));
-}
-
-void Engine::progress_d2h(bool& did_work) {
-  for (size_t i = 0; i < d2h_sends_.size();) {
-    D2hSend* p = d2h_sends_[i].get();
-    std::string err;
-    int r = gpu::poll_ticket(p->ticket, &err);
-    if (r == 0) {
-      i++;
-      continue;
-    }
-    did_work = true;
-    Op* op = p->op;
-    gpu::free_ticket(p->ticket);
-    gpu_sends_.erase(op->id);
-    release_window(op);
-    if (r > 0 && op->conn && !op->conn->dead) {
-      Connection* c = op->conn;
-      TxItem item;
-      FrameHeader h{};
-      h.magic = kMagic;
-      h.type = FT_EAGER;
-      h.tag = op->tag;
-      h.size = op->buf.size;
-      h.op_id = op->id;
-      h.aux = op->buf.size;
-      item.head.resize(sizeof(h));
-      memcpy(item.head.data(), &h, sizeof(h));
-      item.ext_own = std::move(p->buf);
-      item.ext = item.ext_own.data();
-      item.ext_len = op->buf.size;
-      item.is_data = true;
-      item.via_ring = c->shm_tx_enq;
-      c->tx_enqueued_bytes += item.head.size() + item.ext_len;
-      c->txq.push_back(std::move(item));
-      bool dummy = false;
-      handle_writable(c, dummy);
-      // Flushes that snapshot this op id now wait for the wire bytes; the
-      // payload is captured in the frame => the send completes here.
-      on_send_wire_handoff(op, c);
-      Completion comp;
-      comp.kind = Completion::Kind::SendDone;
-      comp.op = op;
-      complete(std::move(comp));
-    } else {
-      for (Op* f : pending_flushes_) f->flush_ops_pending.erase(op->id);
-      fail_op(op, r > 0 ? "send failed: connection reset"
-                        : "send failed: " + err);
-    }
-    d2h_sends_.erase(d2h_sends_.begin() + i);
-  }
-}
-
-// Chunked process_vm_readv pulls, interleaved with the progress loop so a
-// multi-GiB pull never starves other connections; aborted when the sender
-// dies (its memory is gone — the message is lost, recv re-posts, exactly
-// the unflushed-close contract).
-void Engine::progress_cma(bool& did_work) {
-  constexpr size_t kChunk = 8 << 20;
-  for (size_t i = 0; i < cma_pulls_.size();) {
-    CmaPull* p = cma_pulls_[i].get();
-    if (p->conn && p->conn->dead) {
-      repost_recv_front(p->recv_op);  // data lost; recv stays pending
-      cma_pulls_.erase(cma_pulls_.begin() + i);
-      continue;
-    }
-    size_t want = (size_t)std::min<uint64_t>(kChunk, p->size - p->done);
-    uint8_t* dst_base =
-        p->bounce.size() ? p->bounce.data() : p->recv_op->buf.ptr;
-    struct iovec liov {dst_base + p->done, want};
-    struct iovec riov {(void*)(uintptr_t)(p->desc.addr + p->done), want};
-    ssize_t n;
-    static const bool force_eperm =
-        getenv("STARWAY_CMA_FORCE_EPERM") != nullptr;  // test hook
-    if (force_eperm) {
-      errno = EPERM;
-      n = -1;
-    } else {
-      n = process_vm_readv((pid_t)p->desc.pid, &liov, 1, &riov, 1, 0);
-    }
-    if (n < 0 && getenv("STARWAY_DEBUG_CMA"))
-      fprintf(stderr, "[sw-cma] readv pid=%llu addr=%llx want=%zu errno=%d (%s)\n",
-              (unsigned long long)p->desc.pid,
-              (unsigned long long)(p->desc.addr + p->done), want, errno,
-              strerror(errno));
-    if (n < 0) {
-      if (errno == EPERM || errno == ENOSYS) {
-        // No ptrace rights to the sender (e.g. yama scope: a child cannot
-        // read its parent). Tell the sender to retransmit as eager and
-        // RE-POST the recv so the retransmission matches it.
-        std::string err =
-            "cma unavailable (" + std::string(strerror(errno)) + ")";
-        enqueue_frame(p->conn, FT_RECV_FAIL, 0, p->sender_op_id, 0,
-                      err.data(), err.size(), true);
-        repost_recv_front(p->recv_op);
-      } else {
-        // ESRCH/EFAULT: sender died or freed the buffer mid-pull — the
-        // message is lost; the recv stays pending (unflushed-close
-        // contract).
-        repost_recv_front(p->recv_op);
-      }
-      cma_pulls_.erase(cma_pulls_.begin() + i);
-      continue;
-    }
-    did_work = true;
-    p->done += (uint64_t)n;
-    if (p->done >= p->size) {
-      // Data is out of the sender's address space => ack now (the sender
-      // may reuse/free its buffer); any device upload is local work.
-      enqueue_frame(p->conn, FT_RECV_DONE, 0, p->sender_op_id, 0, nullptr, 0,
-                    true);
-      stats_.cma_rx.fetch_add(1, std::memory_order_relaxed);
-      if (p->bounce.size()) {
-        // Device recv: upload the bounce; the recv completes with the h2d
-        // ticket (poll_gpu), which also owns the bounce's lifetime.
-        std::string err;
-        void* ticket =
-            gpu::begin_h2d(p->recv_op->buf, p->bounce.data(), p->size, &err);
-        if (!ticket) {
-          fail_op(p->recv_op, "receive failed: " + err);
-        } else {
-          auto gp = std::make_unique<GpuPull>();
-          gp->ticket = ticket;
-          gp->recv_op = p->recv_op;
-          gp->conn = nullptr;
-          gp->sender_op_id = 0;
-          gp->tag = p->tag;
-          gp->len = p->size;
-          gpu::attach_bounce(ticket, std::move(p->bounce));
-          gpu_pulls_.push_back(std::move(gp));
-        }
-        cma_pulls_.erase(cma_pulls_.begin() + i);
-        continue;
-      }
-      stats_.msgs_received.fetch_add(1, std::memory_order_relaxed);
-      stats_.bytes_received.fetch_add(p->size, std::memory_order_relaxed);
-      Completion comp;
-      comp.kind = Completion::Kind::RecvDone;
-      comp.op = p->recv_op;
-      comp.a = p->tag;
-      comp.b = p->size;
-      complete(std::move(comp));
-      cma_pulls_.erase(cma_pulls_.begin() + i);
-      continue;
-    }
-    i++;
-  }
-}
-
-void Engine::poll_gpu(bool& did_work) {
-  for (size_t i = 0; i < gpu_pulls_.size();) {
-    GpuPull* p = gpu_pulls_[i].get();
-    std::string err;
-    int r = gpu::poll_ticket(p->ticket, &err);
-    if (r == 0) {
-      i++;
-      continue;
-    }
-    did_work = true;
-    if (!p->batch.empty()) {
-      for (auto& it : p->batch) {
-        if (r > 0) {
-          if (it.sender_op_id && it.conn && !it.conn->dead)
-            enqueue_frame(it.conn, FT_RECV_DONE, 0, it.sender_op_id, 0,
-                          nullptr, 0, true);
-          stats_.msgs_received.fetch_add(1, std::memory_order_relaxed);
-          stats_.bytes_received.fetch_add(it.size,
-                                          std::memory_order_relaxed);
-          stats_.gpu_rx.fetch_add(1, std::memory_order_relaxed);
-          Completion comp;
-          comp.kind = Completion::Kind::RecvDone;
-          comp.op = it.recv_op;
-          comp.a = it.tag;
-          comp.b = it.size;
-          complete(std::move(comp));
-        } else {
-          if (it.sender_op_id && it.conn && !it.conn->dead)
-            enqueue_frame(it.conn, FT_RECV_FAIL, 0, it.sender_op_id, 0,
-                          err.data(), err.size(), true);
-          fail_op(it.recv_op, "receive failed: " + err);
-        }
-      }
-    } else if (r > 0) {
-      if (p->sender_op_id && p->conn && !p->conn->dead)
-        enqueue_frame(p->conn, FT_RECV_DONE, 0, p->sender_op_id, 0, nullptr, 0,
-                      true);
-      stats_.msgs_received.fetch_add(1, std::memory_order_relaxed);
-      stats_.bytes_received.fetch_add(p->len, std::memory_order_relaxed);
-      stats_.gpu_rx.fetch_add(1, std::memory_order_relaxed);
-      Completion comp;
-      comp.kind = Completion::Kind::RecvDone;
-      comp.op = p->recv_op;
-      comp.a = p->tag;
-      comp.b = p->len;
-      complete(std::move(comp));
-    } else {
-      if (p->sender_op_id && p->conn && !p->conn->dead)
-        enqueue_frame(p->conn, FT_RECV_FAIL, 0, p->sender_op_id, 0, err.data(),
-                      err.size(), true);
-      fail_op(p->recv_op, "receive failed: " + err);
-    }
-    gpu::free_ticket(p->ticket);
-    gpu_pulls_.erase(gpu_pulls_.begin() + i);
-  }
-}
-
-void Engine::on_gpu_send_acked(uint64_t op_id, bool failed,
-                               const std::string& err) {
-  auto it = gpu_sends_.find(op_id);
-  if (it == gpu_sends_.end()) return;
-  Op* op = it->second;
-  gpu_sends_.erase(it);
-  release_window(op);
-  if (failed && op->buf.device < 0 &&
-      err.find("cma unavailable") != std::string::npos && op->conn &&
-      !op->conn->dead) {
-    op->conn->cma_denied = true;  // stop offering CMA on this connection
-    // Receiver cannot process_vm_readv us (e.g. yama ptrace restrictions):
-    // retransmit the message as a plain eager stream (the captured
-    // snapshot, when present, becomes the frame body). The send op already
-    // completed (handed off); extend any pending flush that covered it to
-    // the new write target so flush still means delivery.
-    bool captured = enqueue_eager(op->conn, op);
-    on_send_wire_handoff(op, op->conn);
-    if (captured) {
-      Completion comp;  // silent completion: callbacks already consumed
-      comp.kind = Completion::Kind::SendDone;
-      comp.op = op;
-      complete(std::move(comp));
-    }
-    // else: the TxItem owns the op and reaps it at write-out (its
-    // callbacks are already consumed, so the completion is silent there).
-    return;
-  }
-  if (failed) {
-    fail_op(op, "send failed: " + err);
-  } else {
-    Completion comp;
-    comp.kind = Completion::Kind::SendDone;
-    comp.op = op;
-    complete(std::move(comp));
-  }
-  // Unblock flushes waiting on this op.
-  for (size_t i = 0; i < pending_flushes_.size();) {
-    Op* f = pending_flushes_[i];
-    f->flush_ops_pending.erase(op_id);
-    if (f->flush_write_targets.empty() && f->flush_ops_pending.empty()) {
-      Completion comp;
-      comp.kind = Completion::Kind::FlushDone;
-      comp.op = f;
-      complete(std::move(comp));
-      pending_flushes_.erase(pending_flushes_.begin() + i);
-    } else {
-      i++;
-    }
-  }
-}
-
-// ---- recv matching --------------------------------------------------------
-
-// STARWAY_UNEXP_CAP: per-connection unexpected-staging receive window
-// (0 disables). Chosen well above the test suite's 32 MiB staging cases
-// but far below RAM scale.
-static uint64_t unexp_cap() {
-  static const uint64_t cap = env_u64("STARWAY_UNEXP_CAP", 512ull << 20);
-  return cap;
-}
-
-void Engine::unstage_unexp(UnexpectedMsg* um) {
-  if (!um->staged) return;
-  if (um->conn) um->conn->unexp_staged_bytes -= um->staged;
-  stats_.unexp_staged_bytes.fetch_sub(um->staged, std::memory_order_relaxed);
-  um->staged = 0;
-}
-
-// Resolve a doorbell conflict: another delivery path selected the armed
-// recv. Cancel the wait kernel and see who won. Returns true when the recv
-// is still available; false when the kernel consumed a message into it
-// first (armed_done_ records the copy until its SMSG frame arrives).
-// Free an armed ticket, or park it as a zombie while its kernel could
-// still write the result cell (launch-queue backlog).
-void Engine::retire_armed_ticket(void* t) {
-  uint64_t sz = 0;
-  if (gpu::arm_poll(t, &sz) != 0)
-    gpu::arm_free(t);
-  else
-    zombie_arms_.push_back(t);
-}
-
-void Engine::poll_zombie_arms() {
-  for (size_t i = 0; i < zombie_arms_.size();) {
-    uint64_t sz = 0;
-    if (gpu::arm_poll(zombie_arms_[i], &sz) != 0) {
-      gpu::arm_free(zombie_arms_[i]);
-      zombie_arms_.erase(zombie_arms_.begin() + i);
-    } else {
-      i++;
-    }
-  }
-}
-
-bool Engine::steal_armed(Op* r) {
-  gpu::arm_cancel(armed_.ticket);
-  uint64_t sz = 0;
-  int st;
-  auto deadline =
-      std::chrono::steady_clock::now() + std::chrono::milliseconds(100);
-  while ((st = gpu::arm_poll(armed_.ticket, &sz)) == 0) {
-    if (std::chrono::steady_clock::now() > deadline) break;
-    sched_yield();
-  }
-  bool copied = (st == 1);
-  retire_armed_ticket(armed_.ticket);
-  Connection* conn = armed_.conn;
-  uint64_t seq = armed_.seq;
-  armed_ = Armed{};
-  if (!copied) return true;
-  // The kernel copied message `seq` into r before we could cancel: r is
-  // spoken for; complete it when the control frame (with the tag) lands.
-  for (auto it = posted_recvs_.begin(); it != posted_recvs_.end(); ++it) {
-    if (*it == r) {
-      posted_recvs_.erase(it);
-      break;
-    }
-  }
-  armed_done_ = ArmedDone{true, conn, seq, sz, r};
-  return false;
-}
-
-// Find and REMOVE the first posted recv matching `tag`, resolving doorbell
-// conflicts. Every delivery path matches through here so the doorbell can
-// never race a completion.
-Op* Engine::take_matching_recv(uint64_t tag) {
-restart:
-  for (auto it = posted_recvs_.begin(); it != posted_recvs_.end(); ++it) {
-    Op* r = *it;
-    if ((tag & r->tag_mask) != (r->tag & r->tag_mask)) continue;
-    if (armed_.ticket && armed_.recv_op == r) {
-      if (!steal_armed(r)) goto restart;  // doorbell consumed r: rescan
-      // steal_armed left r posted; the iterator may be stale — rescan.
-      for (auto it2 = posted_recvs_.begin(); it2 != posted_recvs_.end();
-           ++it2) {
-        if (*it2 == r) {
-          posted_recvs_.erase(it2);
-          return r;
-        }
-      }
-      goto restart;
-    }
-    posted_recvs_.erase(it);
-    return r;
-  }
-  return nullptr;
-}
-
-void Engine::repost_recv_front(Op* r) {
-  if (armed_.ticket) {
-    // The front of the posted queue is changing: the armed recv is no
-    // longer the first match candidate, so the doorbell must stand down.
-    Op* armed_r = armed_.recv_op;
-    if (!steal_armed(armed_r)) {
-      // It consumed a message meanwhile; armed_done_ tracks it.
-    }
-  }
-  posted_recvs_.push_front(r);
-}
-
-void Engine::match_or_stash_recv(Op* op) {
-  arm_streak_ = 0;
-  arm_backoff_ = false;  // fresh recv: the doorbell may re-engage
-  if (!try_match_unexpected(op)) posted_recvs_.push_back(op);
-}
-
-bool Engine::try_match_unexpected(Op* op) {
-  for (auto it = unexpected_.begin(); it != unexpected_.end(); ++it) {
-    UnexpectedMsg* um = it->get();
-    if (um->bound_recv) continue;
-    if ((um->tag & op->tag_mask) != (op->tag & op->tag_mask)) continue;
-    if (um->is_rts) {
-      RtsDesc rts = um->rts;
-      uint64_t tag = um->tag, size = um->size, sop = um->sender_op_id;
-      Connection* c = um->conn;
-      unexpected_.erase(it);
-      start_gpu_pull(op, rts, tag, size, sop, c);
-      return true;
-    }
-    if (um->is_cma) {
-      CmaDesc cma = um->cma;
-      uint64_t tag = um->tag, size = um->size, sop = um->sender_op_id;
-      Connection* c = um->conn;
-      unexpected_.erase(it);
-      start_cma_pull(op, cma, tag, size, sop, c);
-      return true;
-    }
-    if (um->is_smsg) {
-      Connection* c = um->conn;
-      uint64_t tag = um->tag, size = um->size, seq = um->smsg_seq;
-      unexpected_.erase(it);
-      dispatch_smsg_to_recv(c, op, tag, size, seq);
-      return true;
-    }
-    if (!um->complete) {
-      um->bound_recv = op;  // delivered when the stream finishes
-      if (op->buf.device < 0 && um->size <= op->buf.size) {
-        // Redirect: staged prefix now, remainder streams zero-copy.
-        memcpy(op->buf.ptr, um->data.data(), um->got);
-        um->redirect_dst = op->buf.ptr;
-        um->data.clear();
-        unstage_unexp(um);
-      }
-      return true;
-    }
-    UnexpectedMsg* owned = it->release();
-    unexpected_.erase(it);
-    complete_recv_from_unexpected(op, owned);
-    return true;
-  }
-  return false;
-}
-
-void Engine::complete_recv_from_unexpected(Op* op, UnexpectedMsg* um) {
-  std::unique_ptr<UnexpectedMsg> guard(um);
-  unstage_unexp(um);
-  if (um->redirect_dst) {
-    // Stream was redirected into the recv buffer; payload already in place.
-    Completion comp;
-    comp.kind = Completion::Kind::RecvDone;
-    comp.op = op;
-    comp.a = um->tag;
-    comp.b = um->size;
-    complete(std::move(comp));
-    return;
-  }
-  if (um->size > op->buf.size) {
-    fail_op(op, "receive failed: message truncated (len " +
-                    std::to_string(um->size) + " > buffer " +
-                    std::to_string(op->buf.size) + ")");
-    return;
-  }
-  if (op->buf.device >= 0) {
-    std::string err;
-    void* ticket = gpu::begin_h2d(op->buf, um->data.data(), um->size, &err);
-    if (!ticket) {
-      fail_op(op, "receive failed: " + err);
-      return;
-    }
-    auto pull = std::make_unique<GpuPull>();
-    pull->ticket = ticket;
-    pull->recv_op = op;
-    pull->conn = nullptr;
-    pull->sender_op_id = 0;
-    pull->tag = um->tag;
-    pull->len = um->size;
-    gpu::attach_bounce(ticket, std::move(um->data));
-    gpu_pulls_.push_back(std::move(pull));
-    return;
-  }
-  memcpy(op->buf.ptr, um->data.data(), um->size);
-  stats_.msgs_received.fetch_add(1, std::memory_order_relaxed);
-  stats_.bytes_received.fetch_add(um->size, std::memory_order_relaxed);
-  stats_.eager_rx.fetch_add(1, std::memory_order_relaxed);
-  Completion comp;
-  comp.kind = Completion::Kind::RecvDone;
-  comp.op = op;
-  comp.a = um->tag;
-  comp.b = um->size;
-  complete(std::move(comp));
-}
-
-// ---- tx -------------------------------------------------------------------
-
-void Engine::enqueue_frame(Connection* c, FrameType t, uint64_t tag,
-                           uint64_t op_id, uint64_t aux, const void* payload,
-                           size_t payload_len, bool priority,
-                           uint16_t flags) {
-  if (c->dead) return;
-  TxItem item;
-  item.head.resize(sizeof(FrameHeader) + payload_len);
-  FrameHeader h{};
-  h.magic = kMagic;
-  h.type = t;
-  h.flags = flags;
-  h.tag = tag;
-  h.size = payload_len;
-  h.op_id = op_id;
-  h.aux = aux;
-  memcpy(item.head.data(), &h, sizeof(h));
-  if (payload_len) memcpy(item.head.data() + sizeof(h), payload, payload_len);
-  item.is_data = (t == FT_RTS);
-  item.via_ring = c->shm_tx_enq;
-  item.priority = priority;
-  c->tx_enqueued_bytes += item.head.size();
-  if (priority && !c->txq.empty()) {
-    // Insert at a frame boundary: past the partially-written front frame
-    // and past every already-queued priority frame, so priority control
-    // frames keep their relative order and never jump a queued handshake
-    // marker (SHM_ACK/SHM_SWITCH "last TCP frame" invariant).
-    size_t pos = c->tx_front_written > 0 ? 1 : 0;
-    while (pos < c->txq.size() && c->txq[pos].priority) pos++;
-    c->txq.insert(c->txq.begin() + pos, std::move(item));
-  } else {
-    c->txq.push_back(std::move(item));
-  }
-  bool dummy = false;
-  handle_writable(c, dummy);  // opportunistic immediate write
-}
-
-bool Engine::enqueue_eager(Connection* c, Op* op) {
-  TxItem item;
-  static const size_t kInline = env_u64("STARWAY_EAGER_INLINE", 4096);
-  FrameHeader h{};
-  h.magic = kMagic;
-  h.type = FT_EAGER;
-  h.tag = op->tag;
-  h.size = op->buf.size;
-  h.op_id = op->id;
-  h.aux = op->buf.size;
-  item.is_data = true;
-  item.via_ring = c->shm_tx_enq;
-  if (op->capture.size()) {
-    // Retransmission of an already-captured payload (CMA fallback): the
-    // snapshot becomes the frame body, zero extra copies.
-    item.head.resize(sizeof(h));
-    memcpy(item.head.data(), &h, sizeof(h));
-    item.ext_own = std::move(op->capture);
-    item.ext = item.ext_own.data();
-    item.ext_len = op->buf.size;
-  } else if (op->buf.size <= kInline) {
-    item.head.resize(sizeof(h) + op->buf.size);
-    memcpy(item.head.data(), &h, sizeof(h));
-    memcpy(item.head.data() + sizeof(h), op->buf.ptr, op->buf.size);
-  } else {
-    item.head.resize(sizeof(h));
-    memcpy(item.head.data(), &h, sizeof(h));
-    item.ext = op->buf.ptr;
-    item.ext_len = op->buf.size;
-    item.has_keepalive = true;
-    item.keepalive = std::move(op->keepalive);  // moved, no refcount touch
-  }
-  c->tx_enqueued_bytes += item.head.size() + item.ext_len;
-  c->txq.push_back(std::move(item));
-  bool dummy = false;
-  handle_writable(c, dummy);
-  // Capture-on-completion: if the zero-copy frame was not fully written by
-  // the opportunistic write above, snapshot the unwritten remainder into
-  // engine-owned memory before the send completes, so no live pointer into
-  // the caller's buffer survives completion (buffer-reuse contract).
-  if (!c->txq.empty()) {
-    TxItem& back = c->txq.back();
-    if (back.ext && back.ext_own.empty() && back.ext == op->buf.ptr) {
-      size_t off = 0;
-      if (&back == &c->txq.front() && c->tx_front_written > back.head.size())
-        off = c->tx_front_written - back.head.size();
-      // Capture ceiling (STARWAY_CAPTURE_MAX, default 1 GiB): above it a
-      // snapshot would double resident memory, so completion defers to
-      // write-out instead (still reuse-safe — the buffer is pinned and
-      // the caller's await resolves only once the bytes left).
-      static const uint64_t kCaptureMax =
-          env_u64("STARWAY_CAPTURE_MAX", 1ull << 30);
-      if (back.ext_len - off > kCaptureMax) {
-        back.owner = op;
-        return false;
-      }
-      if (back.ext_own.alloc(back.ext_len)) {
-        memcpy(back.ext_own.data() + off, back.ext + off, back.ext_len - off);
-        back.ext = back.ext_own.data();
-        if (back.has_keepalive) {
-          dead_objs_.push_back(std::move(back.keepalive));
-          back.has_keepalive = false;
-        }
-      } else {
-        // Snapshot allocation failed (enormous payload under memory
-        // pressure): keep zero-copy and defer completion to write-out.
-        back.owner = op;
-        return false;
-      }
-    }
-  }
-  return true;
-}
-
-void Engine::handle_writable(Connection* c, bool& did_work) {
-  while (!c->txq.empty() && !c->dead) {
-    TxItem& it = c->txq.front();
-    size_t head_off = std::min(c->tx_front_written, it.head.size());
-    size_t ext_off = c->tx_front_written - head_off;
-    struct iovec iov[2];
-    int nio = 0;
-    if (head_off < it.head.size()) {
-      iov[nio].iov_base = it.head.data() + head_off;
-      iov[nio].iov_len = it.head.size() - head_off;
-      nio++;
-    }
-    if (it.ext && ext_off < it.ext_len) {
-      iov[nio].iov_base = (void*)(it.ext + ext_off);
-      iov[nio].iov_len = it.ext_len - ext_off;
-      nio++;
-    }
-    if (nio == 0) {
-      // fully written
-    } else if (it.via_ring) {
-      size_t wrote = 0;
-      for (int k = 0; k < nio; k++) {
-        size_t n = c->shm->tx.write(iov[k].iov_base, iov[k].iov_len);
-        wrote += n;
-        if (n < iov[k].iov_len) break;  // ring full
-      }
-      if (wrote == 0) return;  // consumer will drain; retried by the loop
-      did_work = true;
-      c->tx_front_written += wrote;
-      c->tx_written_bytes += (uint64_t)wrote;
-    } else {
-      ssize_t n = ::writev(c->fd, iov, nio);
-      if (n < 0) {
-        if (errno == EAGAIN || errno == EWOULDBLOCK) return;
-        on_conn_dead(c);
-        return;
-      }
-      did_work = true;
-      c->tx_front_written += (size_t)n;
-      c->tx_written_bytes += (uint64_t)n;
-    }
-    if (c->tx_front_written >= it.head.size() + it.ext_len) {
-      if (it.has_keepalive) {
-        dead_objs_.push_back(std::move(it.keepalive));
-        it.has_keepalive = false;
-      }
-      if (it.owner) {
-        // Deferred-completion eager send: payload now fully on the wire.
-        Completion comp;
-        comp.kind = Completion::Kind::SendDone;
-        comp.op = it.owner;
-        it.owner = nullptr;
-        complete(std::move(comp));
-      }
-      c->txq.pop_front();
-      c->tx_front_written = 0;
-    } else {
-      return;  // kernel buffer full
-    }
-  }
-}
-
-// ---- flush ----------------------------------------------------------------
-
-void Engine::check_flush_progress() {
-  for (size_t i = 0; i < pending_flushes_.size();) {
-    Op* f = pending_flushes_[i];
-    for (auto it = f->flush_write_targets.begin();
-         it != f->flush_write_targets.end();) {
-      if (it->first->tx_written_bytes >= it->second)
-        it = f->flush_write_targets.erase(it);
-      else
-        ++it;
-    }
-    if (f->flush_write_targets.empty() && f->flush_ops_pending.empty()) {
-      Completion comp;
-      comp.kind = Completion::Kind::FlushDone;
-      comp.op = f;
-      complete(std::move(comp));
-      pending_flushes_.erase(pending_flushes_.begin() + i);
-    } else {
-      i++;
-    }
+    // Payload written or captured => complete now (eager semantics);
+    // else the TxItem owns the op and completion fires at write-out.
+    if (captured) complete_send(op);
   }
 }
 
@@ -2976,20 +692,7 @@ void Engine::on_conn_dead(Connection* c) {
   // receive window of a connection that no longer reads.
   for (auto& um : unexpected_)
     if (um->conn == c) unstage_unexp(um.get());
-  // Drop queued tx (deferring py keepalive refs; failing deferred-
-  // completion owners — their payload never made the wire).
-  for (auto& item : c->txq) {
-    if (item.has_keepalive) {
-      dead_objs_.push_back(std::move(item.keepalive));
-      item.has_keepalive = false;
-    }
-    if (item.owner) {
-      fail_op(item.owner, "send failed: connection reset");
-      item.owner = nullptr;
-    }
-  }
-  c->txq.clear();
-  c->tx_front_written = 0;
+  drop_txq(c, "send failed: connection reset");
   // Release the shm channel now (marks our tx ring closed so the peer sees
   // EOF; the creator unlinks the segment name — the peer's own mapping
   // stays valid until it unmaps).
@@ -2998,24 +701,15 @@ void Engine::on_conn_dead(Connection* c) {
   c->shm.reset();
   // Flushes whose write target on this conn was not reached can never
   // complete: fail them.
-  for (size_t i = 0; i < pending_flushes_.size();) {
-    Op* f = pending_flushes_[i];
-    auto it = f->flush_write_targets.find(c);
-    bool hit = false;
-    if (it != f->flush_write_targets.end()) {
-      if (c->tx_written_bytes >= it->second) {
+  fail_flushes_where(
+      [c](Op* f) {
+        auto it = f->flush_write_targets.find(c);
+        if (it == f->flush_write_targets.end()) return false;
+        if (c->tx_written_bytes < it->second) return true;
         f->flush_write_targets.erase(it);  // satisfied before death
-      } else {
-        hit = true;
-      }
-    }
-    if (hit) {
-      fail_op(f, "flush failed: connection reset");
-      pending_flushes_.erase(pending_flushes_.begin() + i);
-    } else {
-      i++;
-    }
-  }
+        return false;
+      },
+      "flush failed: connection reset");
   // GPU sends routed to this conn will never be acked. Ops owned by the
   // d2h/push staging lists are only unregistered here — their machinery
   // reaps them (double-delete hazard otherwise). Collect the op ids so
@@ -3038,24 +732,28 @@ void Engine::on_conn_dead(Connection* c) {
   }
   c->deferred_sends.clear();
   c->inflight_rndv_bytes = 0;
-  if (!dead_send_ids.empty()) {
-    for (size_t i = 0; i < pending_flushes_.size();) {
-      Op* f = pending_flushes_[i];
-      bool hit = false;
-      for (uint64_t id : dead_send_ids)
-        if (f->flush_ops_pending.erase(id)) hit = true;
-      if (hit) {
-        fail_op(f, "flush failed: connection reset");
-        pending_flushes_.erase(pending_flushes_.begin() + i);
-      } else {
-        i++;
-      }
+  if (!dead_send_ids.empty())
+    fail_flushes_where(
+        [&](Op* f) { return flush_forgets_any(f, dead_send_ids); },
+        "flush failed: connection reset");
+}
+
+// Drop a connection's queued tx: py keepalive refs wait for the next GIL
+// hold, deferred-completion owners fail (their payload never made the
+// wire).
+void Engine::drop_txq(Connection* c, const std::string& reason) {
+  for (auto& item : c->txq) {
+    if (item.has_keepalive) {
+      dead_objs_.push_back(std::move(item.keepalive));
+      item.has_keepalive = false;
+    }
+    if (item.owner) {
+      fail_op(item.owner, reason);
+      item.owner = nullptr;
     }
   }
-  if (mode_ == ClientMode && status_.load() == 2) {
-    // Our single connection died: subsequent ops fail, object stays
-    // closable.
-  }
+  c->txq.clear();
+  c->tx_front_written = 0;
 }
 
 // ---- completion plumbing --------------------------------------------------
@@ -3070,6 +768,68 @@ void Engine::fail_op(Op* op, const std::string& reason) {
   comp.op = op;
   comp.error = reason;
   complete(std::move(comp));
+}
+
+// The one place a recv completes successfully: counts the message once
+// (msgs/bytes_received + the plane's counter) and queues the callback.
+// RxPlane::None counts nothing — only the mid-stream redirect uses it.
+void Engine::deliver_recv(Op* r, uint64_t tag, uint64_t len, RxPlane plane) {
+  if (plane != RxPlane::None) {
+    stats_.msgs_received.fetch_add(1, std::memory_order_relaxed);
+    stats_.bytes_received.fetch_add(len, std::memory_order_relaxed);
+  }
+  switch (plane) {
+    case RxPlane::None:
+      break;
+    case RxPlane::Eager:
+      stats_.eager_rx.fetch_add(1, std::memory_order_relaxed);
+      break;
+    case RxPlane::Gpu:
+      stats_.gpu_rx.fetch_add(1, std::memory_order_relaxed);
+      break;
+    case RxPlane::Cma:
+      stats_.cma_rx.fetch_add(1, std::memory_order_relaxed);
+      break;
+    case RxPlane::Doorbell:  // a doorbell delivery is also an inbox one
+      stats_.doorbell_rx.fetch_add(1, std::memory_order_relaxed);
+      [[fallthrough]];
+    case RxPlane::Inbox:
+      stats_.inbox_rx.fetch_add(1, std::memory_order_relaxed);
+      break;
+  }
+  Completion comp;
+  comp.kind = Completion::Kind::RecvDone;
+  comp.op = r;
+  comp.a = tag;
+  comp.b = len;
+  complete(std::move(comp));
+}
+
+void Engine::complete_send(Op* op) {
+  Completion comp;
+  comp.kind = Completion::Kind::SendDone;
+  comp.op = op;
+  complete(std::move(comp));
+}
+
+void Engine::complete_flush(Op* f) {
+  Completion comp;
+  comp.kind = Completion::Kind::FlushDone;
+  comp.op = f;
+  complete(std::move(comp));
+}
+
+void Engine::send_recv_fail(Connection* c, uint64_t sender_op,
+                            const std::string& err) {
+  if (sender_op && c && !c->dead)
+    enqueue_frame(c, FT_RECV_FAIL, 0, sender_op, 0, err.data(), err.size(),
+                  true);
+}
+
+void Engine::reject_rndv(Connection* c, uint64_t sender_op, Op* recv,
+                         const std::string& err) {
+  send_recv_fail(c, sender_op, err);
+  fail_op(recv, "receive failed: " + err);
 }
 
 void Engine::fire_completions() {
@@ -3122,10 +882,9 @@ void Engine::teardown() {
     for (Op* op : cmds) fail_op(op, "operation canceled (endpoint closing)");
   }
   // 1b. Small-message inbox wind-down: stand the doorbell down, launch any
-  //     pending pushes (payload capture for already-completed... no — push
-  //     ops have NOT completed; they are canceled below if their kernel
-  //     cannot finish), and let in-flight push/unpack kernels drain
-  //     (bounded; they are microsecond-scale copies).
+  //     pending pushes (their ops have not completed; they are canceled
+  //     below if their kernel cannot finish), and let in-flight push/unpack
+  //     kernels drain (bounded; they are microsecond-scale copies).
   if (armed_.ticket) {
     Op* r = armed_.recv_op;
     steal_armed(r);
@@ -3137,31 +896,23 @@ void Engine::teardown() {
     fail_op(armed_done_.recv_op, "operation canceled (endpoint closing)");
     armed_done_ = ArmedDone{};
   }
-  {
-    auto zdeadline =
-        std::chrono::steady_clock::now() + std::chrono::seconds(2);
-    while (!zombie_arms_.empty() &&
-           std::chrono::steady_clock::now() < zdeadline) {
-      poll_zombie_arms();
-      if (!zombie_arms_.empty()) sched_yield();
-    }
-    for (void* t : zombie_arms_) gpu::arm_leak(t);
-    zombie_arms_.clear();
-  }
+  wait_while(std::chrono::seconds(2), [&] {
+    if (!zombie_arms_.empty()) poll_zombie_arms();
+    return !zombie_arms_.empty();
+  });
+  for (void* t : zombie_arms_) gpu::arm_leak(t);
+  zombie_arms_.clear();
   for (auto& m : pending_unpacks_)
     fail_op(m.recv_op, "operation canceled (endpoint closing)");
   pending_unpacks_.clear();
   if (!pending_pushes_.empty()) flush_pending_pushes();
   {
-    auto sm_deadline =
-        std::chrono::steady_clock::now() + std::chrono::seconds(5);
-    while ((!push_batches_.empty() || !unpack_batches_.empty()) &&
-           std::chrono::steady_clock::now() < sm_deadline) {
+    wait_while(std::chrono::seconds(5), [&] {
       bool did = false;
       progress_pushes(did);
       progress_unpacks(did);
-      if (!did) sched_yield();
-    }
+      return !push_batches_.empty() || !unpack_batches_.empty();
+    });
     for (auto& b : push_batches_) {
       gpu::push_free(b->ticket);
       for (Op* op : b->ops) {
@@ -3183,15 +934,14 @@ void Engine::teardown() {
   //    pulls finish (bounded; they are plain copies), complete them and
   //    best-effort ack.
   if (!pending_small_pulls_.empty()) flush_small_pulls();
-  auto deadline = std::chrono::steady_clock::now() + std::chrono::seconds(10);
-  while (!gpu_pulls_.empty() &&
-         std::chrono::steady_clock::now() < deadline) {
+  wait_while(std::chrono::seconds(10), [&] {
     bool did = false;
     poll_gpu(did);
-    if (!did) sched_yield();
-  }
+    return !gpu_pulls_.empty();
+  });
   for (auto& p : gpu_pulls_) {
-    fail_op(p->recv_op, "operation canceled (endpoint closing)");
+    for (auto& it : p->items)
+      fail_op(it.recv_op, "operation canceled (endpoint closing)");
     gpu::free_ticket(p->ticket);
   }
   gpu_pulls_.clear();
@@ -3200,19 +950,14 @@ void Engine::teardown() {
   cma_pulls_.clear();
   // The async D2H copies write into the staging RawBufs below — wait for
   // their tickets (bounded) before freeing them.
-  {
-    auto d2h_deadline =
-        std::chrono::steady_clock::now() + std::chrono::seconds(10);
-    bool pending = true;
-    while (pending && std::chrono::steady_clock::now() < d2h_deadline) {
-      pending = false;
-      for (auto& p : d2h_sends_) {
-        std::string err;
-        if (gpu::poll_ticket(p->ticket, &err) == 0) pending = true;
-      }
-      if (pending) sched_yield();
+  wait_while(std::chrono::seconds(10), [&] {
+    bool pending = false;
+    for (auto& p : d2h_sends_) {
+      std::string err;
+      if (gpu::poll_ticket(p->ticket, &err) == 0) pending = true;
     }
-  }
+    return pending;
+  });
   for (auto& p : d2h_sends_) {
     gpu::free_ticket(p->ticket);
     gpu_sends_.erase(p->op->id);
@@ -3262,7 +1007,8 @@ void Engine::teardown() {
     fail_op(op, "operation canceled (endpoint closing)");
   gpu_sends_.clear();
   // 5. Best-effort drain of remaining control bytes (acks, BYE) ~200 ms.
-  deadline = std::chrono::steady_clock::now() + std::chrono::milliseconds(200);
+  auto deadline =
+      std::chrono::steady_clock::now() + std::chrono::milliseconds(200);
   while (std::chrono::steady_clock::now() < deadline) {
     bool any = false;
     for (auto& c : conns_) {
@@ -3283,17 +1029,7 @@ void Engine::teardown() {
       c->fd = -1;
     }
     if (c->ep) c->ep->conn = nullptr;
-    for (auto& item : c->txq) {
-      if (item.has_keepalive) {
-        dead_objs_.push_back(std::move(item.keepalive));
-        item.has_keepalive = false;
-      }
-      if (item.owner) {
-        fail_op(item.owner, "operation canceled (endpoint closing)");
-        item.owner = nullptr;
-      }
-    }
-    c->txq.clear();
+    drop_txq(c.get(), "operation canceled (endpoint closing)");
     c->shm_rx = false;
     c->shm.reset();
     if (c->inbox_l_active) {

@@ -1,7 +1,7 @@
 // starway_amd._rccl — RCCL-backed multi-endpoint fan-out.
 //
-// The engine's tagged path (engine.cpp) delivers each message with one
-// hipIpc pull over a single xGMI link. For all-pairs / collective-shaped
+// The engine's tagged path (engine_planes.cpp) delivers each message with
+// one hipIpc pull over a single xGMI link. For all-pairs / collective-shaped
 // patterns RCCL's ncclSend/ncclRecv groups schedule traffic across all 7
 // xGMI links per MI355X and route around busy links, so a mesh of
 // endpoints can saturate the full ~1 TB/s per-GPU aggregate. This module

@@ -5,7 +5,7 @@
 // the engine's hot poll loop consumes them, so a same-host frame hop
 // costs two memcpys + an atomic instead of a socket round trip.
 //
-// Handover protocol (engine.cpp): server creates the segment after HELLO
+// Handover protocol (engine_wire.cpp): server creates the segment after HELLO
 // when peer host-id matches, sends SHM_OFFER(name) over TCP; client maps
 // it and replies SHM_ACK as its LAST TCP frame (sender-side TxItems carry
 // a per-item channel flag, so the switch point is exact); server then

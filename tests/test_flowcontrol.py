@@ -6,7 +6,8 @@ Pins the MI355X-native engine's completion/windowing semantics:
   caller that overwrites its buffer the moment ``await asend`` returns must
   never corrupt the in-flight message, on both the eager-TCP path and the
   same-host CMA rendezvous path (UCX ucp_tag_send_nbx contract the
-  reference inherited; see csrc/engine.cpp start_send/enqueue_eager)
+  reference inherited; see csrc/engine.cpp start_send, csrc/engine_wire.cpp
+  enqueue_eager)
 * STARWAY_SEND_WINDOW bounds per-connection rendezvous bytes awaiting
   RECV_DONE; excess sends queue and drain in order (288 GB HBM3E sizing,
   BASELINE config 3 wording)
