@@ -15,6 +15,10 @@ struct CopyTuning {
   int nt_unroll;        // >= 8 selects the x8 NT kernel (STARWAY_COPY_UNROLL)
 };
 
+// Which kernel an N-D copy (launch_copy_nd_tuned) runs. Auto is what
+// production uses; the hooks force one so tests and benches reach both.
+enum class CopyNdPath : int { Auto = 0, Generic = 1, Tiled = 2 };
+
 // Environment-derived default (8192 blocks, 64 MiB, x4), read once per
 // process. Host-only: never touches the GPU.
 const CopyTuning& default_copy_tuning();

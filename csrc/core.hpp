@@ -30,6 +30,7 @@
 #include <pybind11/pybind11.h>
 
 #include "copy_tuning.hpp"
+#include "layout.hpp"
 
 namespace py = pybind11;
 
@@ -40,7 +41,7 @@ namespace sw {
 // ---------------------------------------------------------------------------
 
 constexpr uint32_t kMagic = 0x53574159;  // "SWAY"
-constexpr uint32_t kProtoVersion = 2;
+constexpr uint32_t kProtoVersion = 3;  // 3: RtsDesc carries an N-D layout
 
 enum FrameType : uint16_t {
   FT_HELLO = 1,      // payload: PeerInfo blob (both directions on connect)
@@ -108,6 +109,9 @@ struct RtsDesc {
   uint64_t src_rows;
   uint64_t src_row_bytes;
   uint64_t src_stride;
+  // N-D source layout (src_nd.ndim > 0; src_rows is 0 then): any strided
+  // view the three fields above cannot express. See layout.hpp.
+  Layout src_nd;
 };
 #pragma pack(pop)
 
@@ -160,6 +164,8 @@ const uint8_t* process_uuid();  // 16 bytes, stable for this process
 // rows > 0 => 2D-strided device buffer (non-contiguous tensor): the
 // message is rows x row_bytes dense bytes, row r starting at
 // ptr + r*stride; size == rows*row_bytes.
+// nd.ndim > 0 => N-D strided device buffer (layout.hpp): every view the
+// rows form cannot express; rows is 0 then and size is the message size.
 struct BufferRef {
   uint8_t* ptr = nullptr;
   size_t size = 0;
@@ -167,6 +173,18 @@ struct BufferRef {
   uint64_t rows = 0;
   uint64_t row_bytes = 0;
   uint64_t stride = 0;
+  Layout nd{};
+  // One dense run of `size` bytes at ptr. Anything else is packed or
+  // unpacked by a copy kernel: it stays off the inbox push plane and the
+  // doorbell, takes the bounce path for eager/inbox/CMA deliveries and
+  // needs the exact message size.
+  bool dense() const { return rows == 0 && nd.ndim == 0; }
+  // This buffer as a Layout, for a copy whose other side is N-D.
+  Layout layout() const {
+    if (nd.ndim > 0) return nd;
+    if (rows > 0) return rows_layout(rows, row_bytes, stride);
+    return contiguous_layout(size);
+  }
 };
 
 // Uninitialized heap buffer (std::vector zero-fills on resize, which stalls
@@ -784,6 +802,16 @@ bool copy_device_sync(void* dst, const void* src, size_t n, int device,
 bool copy_strided_sync(void* dst, uint64_t dst_stride, const void* src,
                        uint64_t src_stride, uint64_t rows, uint64_t row_bytes,
                        int device, size_t block_cap, std::string* err);
+// N-D copy (k_copy_nd / k_copy_nd_tile). Both layouts describe `bytes`
+// message bytes. *ineligible is set when path == Tiled was asked for a
+// pair outside the transpose family (nothing is launched then).
+bool copy_nd_sync(void* dst, const Layout& dst_layout, const void* src,
+                  const Layout& src_layout, uint64_t bytes, int device,
+                  size_t block_cap, CopyNdPath path, bool* ineligible,
+                  std::string* err);
+// Tile extent (elements, both axes) of k_copy_nd_tile per element size;
+// a compile-time constant of the kernels, 0 for an unsupported size.
+int copy_nd_tile_extent(int elem_bytes);
 struct CopyDesc {
   void* dst;
   const void* src;

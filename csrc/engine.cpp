@@ -571,7 +571,7 @@ void Engine::start_send(Op* op, Connection* c) {
   // FT_SMSG control frame is enqueued HERE so per-connection message order
   // is preserved against eager/RTS traffic. The op completes when the push
   // kernel's event lands (payload captured out of the user buffer).
-  if (inbox_enabled() && op->buf.device >= 0 && op->buf.rows == 0 &&
+  if (inbox_enabled() && op->buf.device >= 0 && op->buf.dense() &&
       op->buf.size > 0 && !force_xhost && c->inbox_r_active &&
       op->buf.size <= c->inbox_r.slot_bytes - gpu::kInboxHdrBytes &&
       c->inbox_next_seq <= c->inbox_credit_base + c->inbox_r.slots) {

@@ -28,7 +28,10 @@ void Engine::handle_rts(Connection* c, const RtsDesc& rts, uint64_t tag,
 
 void Engine::start_gpu_pull(Op* recv_op, const RtsDesc& rts, uint64_t tag,
                             uint64_t size, uint64_t sender_op, Connection* c) {
-  if (size > recv_op->buf.size) {
+  // An N-D window needs the exact message size (a 2-D one too: begin_pull
+  // refuses it with its own geometry text).
+  if (size > recv_op->buf.size ||
+      (recv_op->buf.nd.ndim > 0 && size != recv_op->buf.size)) {
     reject_rndv(c, sender_op, recv_op, truncated_msg(size, recv_op->buf.size));
     return;
   }
@@ -37,7 +40,7 @@ void Engine::start_gpu_pull(Op* recv_op, const RtsDesc& rts, uint64_t tag,
   // iteration (the per-launch cost dominates small-message rate).
   static const uint64_t kMultiMax = env_u64("STARWAY_MULTI_COPY_MAX", 65536);
   if (size > 0 && size <= kMultiMax && recv_op->buf.device >= 0 &&
-      recv_op->buf.rows == 0 && rts.src_rows == 0) {
+      recv_op->buf.dense() && rts.src_rows == 0 && rts.src_nd.ndim == 0) {
     pending_small_pulls_.push_back(
         SmallPull{rts, recv_op, c, sender_op, tag, size});
     return;
@@ -132,13 +135,13 @@ void Engine::inbox_release_seq(Connection* c, uint64_t seq) {
 // unpack kernel (device dst) or pinned bounce (host / strided dst).
 void Engine::dispatch_smsg_to_recv(Connection* c, Op* r, uint64_t tag,
                                    uint64_t size, uint64_t seq) {
-  if (size > r->buf.size || (r->buf.rows > 0 && size != r->buf.size)) {
+  if (size > r->buf.size || (!r->buf.dense() && size != r->buf.size)) {
     fail_op(r, "receive failed: " + truncated_msg(size, r->buf.size));
     inbox_release_seq(c, seq);  // discard without reading the slot
     return;
   }
   uint8_t* dst = nullptr;
-  if (r->buf.device >= 0 && r->buf.rows == 0 &&
+  if (r->buf.device >= 0 && r->buf.dense() &&
       r->buf.device == c->inbox_l.device)
     dst = r->buf.ptr;
   pending_unpacks_.push_back(PendingUnpack{c, seq, size, tag, r, dst});
@@ -418,7 +421,7 @@ void Engine::try_arm() {
   // arm launch + inline wait per message.
   if (posted_recvs_.size() != 1) return;
   Op* r = posted_recvs_.front();
-  if (r->buf.device < 0 || r->buf.rows > 0 || r->buf.size == 0) return;
+  if (r->buf.device < 0 || !r->buf.dense() || r->buf.size == 0) return;
   // Only safe with exactly one live connection (its inbox FIFO is then the
   // only source of inbox messages that could race the doorbell).
   Connection* target = nullptr;
@@ -476,7 +479,7 @@ void Engine::start_cma_pull(Op* recv_op, const CmaDesc& cma, uint64_t tag,
                             uint64_t size, uint64_t sender_op,
                             Connection* c) {
   if (size > recv_op->buf.size ||
-      (recv_op->buf.rows > 0 && size != recv_op->buf.size)) {
+      (!recv_op->buf.dense() && size != recv_op->buf.size)) {
     reject_rndv(c, sender_op, recv_op, truncated_msg(size, recv_op->buf.size));
     return;
   }

@@ -882,7 +882,7 @@ void Engine::begin_eager(Connection* c) {
   if (Op* r = take_matching_recv(tag)) {
     {
       if (msg_len > r->buf.size ||
-          (r->buf.rows > 0 && msg_len != r->buf.size)) {
+          (!r->buf.dense() && msg_len != r->buf.size)) {
         // Truncation / strided-geometry mismatch: consume + fail
         // (UCX MESSAGE_TRUNCATED analog; a strided window needs the exact
         // message size or partial rows would smear).

@@ -39,6 +39,16 @@ hipError_t launch_copy_strided_tuned(void* dst, uint64_t dst_stride,
                                      const void* src, uint64_t src_stride,
                                      uint64_t rows, uint64_t row_bytes,
                                      hipStream_t stream, const CopyTuning& t);
+hipError_t launch_copy_nd(void* dst, const Layout& dst_layout,
+                          const void* src, const Layout& src_layout,
+                          uint64_t bytes, hipStream_t stream);
+hipError_t launch_copy_nd_tuned(void* dst, const Layout& dst_layout,
+                                const void* src, const Layout& src_layout,
+                                uint64_t bytes, hipStream_t stream,
+                                const CopyTuning& t, CopyNdPath path);
+int copy_nd_tile_extent(int elem_bytes);
+bool copy_nd_tile_eligible(const Layout& src_layout, const Layout& dst_layout,
+                           const void* src, const void* dst);
 
 namespace gpu {
 
@@ -359,6 +369,7 @@ bool make_rts(const BufferRef& buf, RtsDesc* out, std::string* err) {
   out->src_rows = buf.rows;
   out->src_row_bytes = buf.row_bytes;
   out->src_stride = buf.stride;
+  out->src_nd = buf.nd;
   // Resolve the allocation base for IPC export.
   int prev;
   hipGetDevice(&prev);
@@ -403,7 +414,51 @@ struct Ticket {
   hipEvent_t ev = nullptr;
   int device = -1;
   RawBuf bounce;  // host staging kept alive until completion
+  // Contiguous device staging of an N-D host<->device transfer; released
+  // with the ticket.
+  void* dev_staging = nullptr;
 };
+
+// hipMemcpy2DAsync cannot express an N-D layout, so a host endpoint of an
+// N-D device buffer goes through a contiguous device staging buffer on the
+// same stream: host -> staging -> k_copy_nd -> destination, or the
+// reverse. Not the hot path (device<->device pulls never stage): a plain
+// hipMalloc per transfer, and a hipFree that may wait for the device.
+static hipError_t alloc_staging(uint64_t size, void** out) {
+  return hipMalloc(out, size ? size : 1);
+}
+
+// Release a staging buffer whose ticket was never handed out; work queued
+// on `stream` may still touch it.
+static void drop_staging(void* staging, hipStream_t stream) {
+  if (!staging) return;
+  hipStreamSynchronize(stream);
+  hipFree(staging);
+}
+
+// The source side of a pull as a Layout, checked against the message size
+// (the descriptor comes from the peer).
+static bool rts_layout(const RtsDesc& rts, uint64_t size, Layout* out,
+                       std::string* err) {
+  try {
+    if (rts.src_nd.ndim > 0) {
+      *out = rts.src_nd;
+      if (out->ndim > kMaxDims || out->unit == 0 ||
+          layout_bytes(*out) != size) {
+        *err = "malformed N-D source layout in RTS";
+        return false;
+      }
+    } else if (rts.src_rows > 0) {
+      *out = rows_layout(rts.src_rows, rts.src_row_bytes, rts.src_stride);
+    } else {
+      *out = contiguous_layout(size);
+    }
+  } catch (const std::invalid_argument& e) {
+    *err = e.what();
+    return false;
+  }
+  return true;
+}
 
 // hipEvent pool per device (create/destroy costs ~1-2 us per op).
 static std::map<int, std::vector<hipEvent_t>> g_event_pool;
@@ -509,6 +564,7 @@ void* begin_pull(const RtsDesc& rts, const BufferRef& dst, uint64_t size,
   int lane = rts.device & (stream_lanes() - 1);
   hipStream_t stream = pull_stream(run_dev, lane);
   hipError_t e;
+  void* staging = nullptr;
   if (dst.device >= 0) {
     bool same_proc = memcmp(rts.src_uuid, process_uuid(), 16) == 0;
     if (same_proc) ensure_peer_access(dst.device, rts.device);
@@ -523,14 +579,31 @@ void* begin_pull(const RtsDesc& rts, const BufferRef& dst, uint64_t size,
     }();
     bool src_strided = rts.src_rows > 0;
     bool dst_strided = dst.rows > 0;
-    if (dst_strided && dst.size != size) {
+    const bool nd = rts.src_nd.ndim > 0 || dst.nd.ndim > 0;
+    if (!dst.dense() && dst.size != size) {
       hipSetDevice(prev);
       *err = "strided recv buffer geometry mismatch (buffer " +
              std::to_string(dst.size) + " B, message " +
              std::to_string(size) + " B)";
       return nullptr;
     }
-    if (src_strided || dst_strided) {
+    if (nd) {
+      // Either side N-D: both are expressed as layouts, and the only
+      // geometry requirement is the total size (checked above).
+      Layout sl{}, dl{};
+      bool ok = rts_layout(rts, size, &sl, err);
+      try {
+        if (ok) dl = dst.dense() ? contiguous_layout(size) : dst.layout();
+      } catch (const std::invalid_argument& ex) {
+        *err = ex.what();
+        ok = false;
+      }
+      if (!ok) {
+        hipSetDevice(prev);
+        return nullptr;
+      }
+      e = launch_copy_nd(dst.ptr, dl, src, sl, size, stream);
+    } else if (src_strided || dst_strided) {
       // Pack/unpack inside the pull kernel. Row geometry: prefer the
       // source's; a strided dst must agree on row_bytes.
       uint64_t rows = src_strided ? rts.src_rows : dst.rows;
@@ -557,7 +630,20 @@ void* begin_pull(const RtsDesc& rts, const BufferRef& dst, uint64_t size,
       e = launch_copy(dst.ptr, src, size, stream);
     }
   } else {
-    if (rts.src_rows > 0) {
+    if (rts.src_nd.ndim > 0) {
+      Layout sl{};
+      if (!rts_layout(rts, size, &sl, err)) {
+        hipSetDevice(prev);
+        return nullptr;
+      }
+      e = alloc_staging(size, &staging);
+      if (e == hipSuccess)
+        e = launch_copy_nd(staging, contiguous_layout(size), src, sl, size,
+                           stream);
+      if (e == hipSuccess)
+        e = hipMemcpyAsync(dst.ptr, staging, size, hipMemcpyDeviceToHost,
+                           stream);
+    } else if (rts.src_rows > 0) {
       e = hipMemcpy2DAsync(dst.ptr, rts.src_row_bytes, src, rts.src_stride,
                            rts.src_row_bytes, rts.src_rows,
                            hipMemcpyDeviceToHost, stream);
@@ -566,17 +652,20 @@ void* begin_pull(const RtsDesc& rts, const BufferRef& dst, uint64_t size,
     }
   }
   if (e != hipSuccess) {
+    drop_staging(staging, stream);
     hipSetDevice(prev);
     *err = std::string("pull launch: ") + hipGetErrorString(e);
     return nullptr;
   }
   Ticket* t = new Ticket();
   t->device = run_dev;
+  t->dev_staging = staging;
   e = pool_get_event(run_dev, &t->ev);
   if (e == hipSuccess) e = hipEventRecord(t->ev, stream);
   hipSetDevice(prev);
   if (e != hipSuccess) {
     *err = std::string("event: ") + hipGetErrorString(e);
+    drop_staging(staging, stream);
     delete t;
     return nullptr;
   }
@@ -639,7 +728,22 @@ void* begin_h2d(const BufferRef& dst, const void* src, uint64_t size,
   hipSetDevice(dst.device);
   hipStream_t stream = pull_stream(dst.device);
   hipError_t e;
-  if (dst.rows > 0) {
+  void* staging = nullptr;
+  if (dst.nd.ndim > 0) {
+    if (size != dst.size) {
+      hipSetDevice(prev);
+      *err = "strided recv buffer geometry mismatch (buffer " +
+             std::to_string(dst.size) + " B, message " +
+             std::to_string(size) + " B)";
+      return nullptr;
+    }
+    e = alloc_staging(size, &staging);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(staging, src, size, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess)
+      e = launch_copy_nd(dst.ptr, dst.nd, staging, contiguous_layout(size),
+                         size, stream);
+  } else if (dst.rows > 0) {
     e = hipMemcpy2DAsync(dst.ptr, dst.stride, src, dst.row_bytes,
                          dst.row_bytes, dst.rows, hipMemcpyHostToDevice,
                          stream);
@@ -653,6 +757,8 @@ void* begin_h2d(const BufferRef& dst, const void* src, uint64_t size,
     e = pool_get_event(dst.device, &t->ev);
     if (e == hipSuccess) e = hipEventRecord(t->ev, stream);
   }
+  if (e == hipSuccess) t->dev_staging = staging;
+  else drop_staging(staging, stream);
   hipSetDevice(prev);
   if (e != hipSuccess) {
     *err = std::string("h2d: ") + hipGetErrorString(e);
@@ -673,7 +779,16 @@ void* begin_d2h(void* host_dst, const BufferRef& src, std::string* err) {
   hipSetDevice(src.device);
   hipStream_t stream = pull_stream(src.device);
   hipError_t e;
-  if (src.rows > 0) {
+  void* staging = nullptr;
+  if (src.nd.ndim > 0) {
+    e = alloc_staging(src.size, &staging);
+    if (e == hipSuccess)
+      e = launch_copy_nd(staging, contiguous_layout(src.size), src.ptr,
+                         src.nd, src.size, stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(host_dst, staging, src.size, hipMemcpyDeviceToHost,
+                         stream);
+  } else if (src.rows > 0) {
     e = hipMemcpy2DAsync(host_dst, src.row_bytes, src.ptr, src.stride,
                          src.row_bytes, src.rows, hipMemcpyDeviceToHost,
                          stream);
@@ -688,6 +803,8 @@ void* begin_d2h(void* host_dst, const BufferRef& src, std::string* err) {
     e = pool_get_event(src.device, &t->ev);
     if (e == hipSuccess) e = hipEventRecord(t->ev, stream);
   }
+  if (e == hipSuccess) t->dev_staging = staging;
+  else drop_staging(staging, stream);
   hipSetDevice(prev);
   if (e != hipSuccess) {
     *err = std::string("d2h: ") + hipGetErrorString(e);
@@ -716,6 +833,7 @@ void free_ticket(void* ticket) {
     std::lock_guard<std::mutex> lk(g_mu);
     pool_put_event(t->device, t->ev);
   }
+  if (t->dev_staging) hipFree(t->dev_staging);
   delete t;
 }
 
@@ -772,6 +890,27 @@ bool copy_strided_sync(void* dst, uint64_t dst_stride, const void* src,
     return launch_copy_strided_tuned(dst, dst_stride, src, src_stride, rows,
                                      row_bytes, stream, t);
   });
+}
+
+bool copy_nd_sync(void* dst, const Layout& dst_layout, const void* src,
+                  const Layout& src_layout, uint64_t bytes, int device,
+                  size_t block_cap, CopyNdPath path, bool* ineligible,
+                  std::string* err) {
+  CopyTuning t = resolve_tuning(CopyTuning{block_cap, 0, 0});
+  *ineligible = path == CopyNdPath::Tiled &&
+                !copy_nd_tile_eligible(src_layout, dst_layout, src, dst);
+  if (*ineligible) {
+    *err = "the tiled kernel does not serve this pair of layouts";
+    return false;
+  }
+  return run_sync(device, err, [&](hipStream_t stream) {
+    return launch_copy_nd_tuned(dst, dst_layout, src, src_layout, bytes,
+                                stream, t, path);
+  });
+}
+
+int copy_nd_tile_extent(int elem_bytes) {
+  return sw::copy_nd_tile_extent(elem_bytes);
 }
 
 // Callers validate 1 <= n <= 8 and bytes < 2^32 (launch_copy_multi does not).

@@ -49,6 +49,14 @@ bool copy_strided_sync(void*, uint64_t, const void*, uint64_t, uint64_t,
   *err = "no GPU (sanitizer stub)";
   return false;
 }
+bool copy_nd_sync(void*, const Layout&, const void*, const Layout&, uint64_t,
+                  int, size_t, CopyNdPath, bool* ineligible,
+                  std::string* err) {
+  *ineligible = false;
+  *err = "no GPU (sanitizer stub)";
+  return false;
+}
+int copy_nd_tile_extent(int) { return 0; }
 bool copy_multi_sync(const CopyDesc*, int, int, std::string* err) {
   *err = "no GPU (sanitizer stub)";
   return false;

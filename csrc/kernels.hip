@@ -23,6 +23,7 @@
 #include <cstdlib>
 
 #include "copy_tuning.hpp"
+#include "layout.hpp"
 
 namespace sw {
 
@@ -322,6 +323,314 @@ hipError_t launch_copy_strided(void* dst, uint64_t dst_stride,
                                hipStream_t stream) {
   return launch_copy_strided_tuned(dst, dst_stride, src, src_stride, rows,
                                    row_bytes, stream, default_copy_tuning());
+}
+
+// ---------------------------------------------------------------------------
+// N-D pack/unpack copy (layout.hpp): any strided view on either side, e.g.
+// a transposed matrix or a (B,H,S,D)->(B,S,H,D) permute. Serves only the
+// layouts the 2-D kernels above cannot express.
+// ---------------------------------------------------------------------------
+
+template <int G> struct GranuleT;
+template <> struct GranuleT<16> { using type = uint4; };
+template <> struct GranuleT<8> { using type = uint2; };
+template <> struct GranuleT<4> { using type = uint32_t; };
+template <> struct GranuleT<2> { using type = uint16_t; };
+template <> struct GranuleT<1> { using type = uint8_t; };
+
+// Byte offset of granule `i` (G = 1 << shift bytes each, message order)
+// from the view's base. G divides unit and every stride, so a granule never
+// straddles a run.
+template <class Idx>
+__device__ __forceinline__ int64_t nd_offset(const Layout& l, Idx i,
+                                             int shift) {
+  if (l.ndim == 0) return (int64_t)((uint64_t)i << shift);
+  const Idx ug = (Idx)(l.unit >> shift);
+  Idx q = i / ug;
+  int64_t off = (int64_t)((uint64_t)(i - q * ug) << shift);
+#pragma unroll
+  for (int d = (int)kMaxDims - 1; d >= 0; --d) {
+    if (d < (int)l.ndim) {
+      const Idx s = (Idx)l.shape[d];
+      const Idx nq = q / s;
+      off += (int64_t)(q - nq * s) * l.stride[d];
+      q = nq;
+    }
+  }
+  return off;
+}
+
+// Generic N-D copy: grid-stride over the message in G-byte granules, in
+// message order; each side's address comes from its own layout. Idx is
+// uint32_t when the host has checked that the granule count (and so every
+// quotient and extent) fits, else uint64_t: 64-bit division costs several
+// times the 32-bit one on gfx950 and this kernel does up to 2*(ndim+1) of
+// them per granule.
+template <int G, class Idx>
+__global__ __launch_bounds__(256) void k_copy_nd(
+    const uint8_t* __restrict__ src, Layout sl, uint8_t* __restrict__ dst,
+    Layout dl, uint64_t n_granules) {
+  using V = typename GranuleT<G>::type;
+  constexpr int shift = __builtin_ctz(G);
+  const Idx n = (Idx)n_granules;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += stride) {
+    const int64_t so = nd_offset<Idx>(sl, (Idx)i, shift);
+    const int64_t dof = nd_offset<Idx>(dl, (Idx)i, shift);
+    *(V*)(dst + dof) = *(const V*)(src + so);
+  }
+}
+
+// Transpose family: one side contiguous (dense along the innermost logical
+// dimension B), the other a layout of single elements whose unit-stride
+// dimension A is not B. A generic copy leaves one side with E-byte accesses
+// a whole stride apart; here a workgroup stages a T x T element tile
+// through LDS, reading with lanes along the source's dense axis and
+// writing with lanes along the destination's. All other dimensions are
+// batch dimensions decoded from the tile index.
+struct TileArgs {
+  uint64_t nA, nB;       // extents of the two tile axes
+  int64_t sB;            // strided side: byte stride of B (A's is E)
+  uint64_t cA;           // contiguous side: byte stride of A (B's is E)
+  uint32_t nbatch;       // batch dimensions, outermost first
+  uint32_t s_is_src;     // strided side is the source
+  uint64_t bshape[3];
+  int64_t bS[3];         // strided side byte strides
+  uint64_t bC[3];        // contiguous side byte strides
+  uint64_t tilesA, tilesB, tiles;  // tiles = tilesA * tilesB * batch
+};
+
+template <int E> struct TileT {
+  static constexpr int T = E == 16 ? 32 : 64;
+  // Row pad: one access width, and at least one bank (4 B) because sub-
+  // dword accesses still bank by dword. Row pitches 68/132/260/520/528 B
+  // put the lanes of the transposed phase on distinct banks.
+  static constexpr int PAD = E < 4 ? 4 : E;
+  static constexpr int PITCH = T * E + PAD;
+};
+
+template <int E>
+__global__ __launch_bounds__(256) void k_copy_nd_tile(
+    const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, TileArgs a) {
+  using V = typename GranuleT<E>::type;
+  constexpr int T = TileT<E>::T;
+  constexpr int PITCH = TileT<E>::PITCH;
+  constexpr int ROWS = 256 / T;  // tile rows covered per pass
+  __shared__ __attribute__((aligned(16))) uint8_t tile[T * PITCH];
+  const int lane = threadIdx.x % T;
+  const int row0 = threadIdx.x / T;
+  for (uint64_t t = blockIdx.x; t < a.tiles; t += gridDim.x) {
+    uint64_t q = t / a.tilesB;
+    const uint64_t b0 = (t - q * a.tilesB) * T;
+    uint64_t bq = q / a.tilesA;
+    const uint64_t a0 = (q - bq * a.tilesA) * T;
+    int64_t offS = 0;
+    uint64_t offC = 0;
+    for (int d = (int)a.nbatch - 1; d >= 0; --d) {
+      const uint64_t nq = bq / a.bshape[d];
+      const uint64_t idx = bq - nq * a.bshape[d];
+      offS += (int64_t)idx * a.bS[d];
+      offC += idx * a.bC[d];
+      bq = nq;
+    }
+    // Element (ia, ib) of the tile: strided side at offS + ia*E + ib*sB,
+    // contiguous side at offC + ia*cA + ib*E.
+    if (a.s_is_src) {
+      // Read with lanes along A; LDS is [ib][ia].
+      const uint64_t ia = a0 + lane;
+      for (int r = row0; r < T; r += ROWS) {
+        const uint64_t ib = b0 + r;
+        if (ia < a.nA && ib < a.nB)
+          *(V*)(tile + r * PITCH + lane * E) =
+              *(const V*)(src + offS + (int64_t)(ia * E) + (int64_t)ib * a.sB);
+      }
+      __syncthreads();
+      // Write with lanes along B.
+      const uint64_t ob = b0 + lane;
+      for (int r = row0; r < T; r += ROWS) {
+        const uint64_t oa = a0 + r;
+        if (oa < a.nA && ob < a.nB)
+          *(V*)(dst + offC + oa * a.cA + ob * E) =
+              *(const V*)(tile + lane * PITCH + r * E);
+      }
+    } else {
+      // Read with lanes along B; LDS is [ia][ib].
+      const uint64_t ib = b0 + lane;
+      for (int r = row0; r < T; r += ROWS) {
+        const uint64_t ia = a0 + r;
+        if (ia < a.nA && ib < a.nB)
+          *(V*)(tile + r * PITCH + lane * E) =
+              *(const V*)(src + offC + ia * a.cA + ib * E);
+      }
+      __syncthreads();
+      // Write with lanes along A.
+      const uint64_t oa = a0 + lane;
+      for (int r = row0; r < T; r += ROWS) {
+        const uint64_t ob = b0 + r;
+        if (oa < a.nA && ob < a.nB)
+          *(V*)(dst + offS + (int64_t)(oa * E) + (int64_t)ob * a.sB) =
+              *(const V*)(tile + lane * PITCH + r * E);
+      }
+    }
+    __syncthreads();  // the next tile overwrites the LDS
+  }
+}
+
+int copy_nd_tile_extent(int elem_bytes) {
+  switch (elem_bytes) {
+    case 1: return TileT<1>::T;
+    case 2: return TileT<2>::T;
+    case 4: return TileT<4>::T;
+    case 8: return TileT<8>::T;
+    case 16: return TileT<16>::T;
+  }
+  return 0;
+}
+
+// Which side is the transposed one, and along which dimension; false when
+// the pair is not in the transpose family or an access would be misaligned.
+static bool tile_plan(const Layout& sl, const Layout& dl, const void* src,
+                      const void* dst, bool* s_is_src, int* axis) {
+  const Layout* s = nullptr;
+  if (sl.ndim == 0 && dl.ndim >= 2) {
+    s = &dl;
+    *s_is_src = false;
+  } else if (dl.ndim == 0 && sl.ndim >= 2) {
+    s = &sl;
+    *s_is_src = true;
+  } else {
+    return false;
+  }
+  *axis = tile_axis(*s);
+  if (*axis < 0) return false;
+  return granule(sl, dl, (uint64_t)(uintptr_t)src, (uint64_t)(uintptr_t)dst) >=
+         s->unit;
+}
+
+bool copy_nd_tile_eligible(const Layout& sl, const Layout& dl, const void* src,
+                           const void* dst) {
+  bool s_is_src;
+  int axis;
+  return tile_plan(sl, dl, src, dst, &s_is_src, &axis);
+}
+
+template <int E>
+static void launch_tile(const uint8_t* src, uint8_t* dst, const TileArgs& a,
+                        size_t cap, hipStream_t stream) {
+  size_t blocks = a.tiles < cap ? (size_t)a.tiles : cap;
+  hipLaunchKernelGGL(k_copy_nd_tile<E>, dim3((unsigned)blocks), dim3(256), 0,
+                     stream, src, dst, a);
+}
+
+template <int G>
+static void launch_nd(const uint8_t* src, const Layout& sl, uint8_t* dst,
+                      const Layout& dl, uint64_t bytes, size_t cap,
+                      hipStream_t stream) {
+  const uint64_t n = bytes / G;
+  const dim3 grid(copy_grid(n / 4 + 1, cap));
+  // 32-bit index arithmetic only where every value fits: the granule
+  // count bounds each quotient and (the message being non-empty) each
+  // extent.
+  if (n <= UINT32_MAX)
+    hipLaunchKernelGGL((k_copy_nd<G, uint32_t>), grid, dim3(256), 0, stream,
+                       src, sl, dst, dl, n);
+  else
+    hipLaunchKernelGGL((k_copy_nd<G, uint64_t>), grid, dim3(256), 0, stream,
+                       src, sl, dst, dl, n);
+}
+
+// Dispatch rule for CopyNdPath::Auto: the tiled kernel whenever the pair is
+// in the transpose family (tile_plan), i.e. the strided side's dense run is
+// a single element (<= 16 B), and dimension A fills at least half a tile
+// row; the generic kernel for everything else.
+//
+// Measured on MI355X, fp16, payload GB/s, median of 7 rounds x 10 calls,
+// two runs within 1 % of each other, rounds within 7 %
+// (docs/benchmark.md "N-D layouts", profiles/nd_layouts_run*.txt):
+//   2-D transpose        generic   tiled   .contiguous()+flat   flat
+//     64 MiB                 466    1288          391           1810
+//     256 MiB                187    1121          431           2373
+//   (B,H,S,D)->(B,S,H,D), D=128: 256 B dense runs, not in the family
+//     64 MiB                1967       -          837           1834
+//     256 MiB               2271       -         1072           2273
+// With 256 B runs the generic kernel already matches the flat copy, so
+// there is nothing for a tiled kernel to win above single elements. The
+// half-row floor is reasoning, not measurement: with fewer elements along A
+// most lanes of the phase that runs along A idle, while the generic
+// kernel's message-order walk keeps the contiguous side coalesced.
+hipError_t launch_copy_nd_tuned(void* dst, const Layout& dl, const void* src,
+                                const Layout& sl, uint64_t bytes,
+                                hipStream_t stream, const CopyTuning& t,
+                                CopyNdPath path) {
+  if (bytes == 0) return hipSuccess;
+  bool s_is_src = false;
+  int axis = -1;
+  const bool eligible = tile_plan(sl, dl, src, dst, &s_is_src, &axis);
+  if (path == CopyNdPath::Tiled && !eligible) return hipErrorInvalidValue;
+  const size_t cap = t.block_cap;
+  if (eligible && path != CopyNdPath::Generic) {
+    const Layout& s = s_is_src ? sl : dl;
+    const int E = (int)s.unit;
+    const int T = copy_nd_tile_extent(E);
+    const int B = (int)s.ndim - 1;
+    if (path == CopyNdPath::Tiled || s.shape[axis] >= (uint64_t)T / 2) {
+      TileArgs a{};
+      a.nA = s.shape[axis];
+      a.nB = s.shape[B];
+      a.sB = s.stride[B];
+      a.s_is_src = s_is_src;
+      // Contiguous-side strides: row-major over the strided side's own
+      // dimensions, which is the message order.
+      uint64_t cstride[kMaxDims];
+      uint64_t run = (uint64_t)E;
+      for (int d = B; d >= 0; --d) {
+        cstride[d] = run;
+        run *= s.shape[d];
+      }
+      a.cA = cstride[axis];
+      uint64_t batch = 1;
+      for (int d = 0; d < B; d++) {
+        if (d == axis) continue;
+        a.bshape[a.nbatch] = s.shape[d];
+        a.bS[a.nbatch] = s.stride[d];
+        a.bC[a.nbatch] = cstride[d];
+        a.nbatch++;
+        batch *= s.shape[d];
+      }
+      a.tilesA = (a.nA + T - 1) / T;
+      a.tilesB = (a.nB + T - 1) / T;
+      a.tiles = a.tilesA * a.tilesB * batch;
+      const uint8_t* sp = (const uint8_t*)src;
+      uint8_t* dp = (uint8_t*)dst;
+      switch (E) {
+        case 1: launch_tile<1>(sp, dp, a, cap, stream); break;
+        case 2: launch_tile<2>(sp, dp, a, cap, stream); break;
+        case 4: launch_tile<4>(sp, dp, a, cap, stream); break;
+        case 8: launch_tile<8>(sp, dp, a, cap, stream); break;
+        default: launch_tile<16>(sp, dp, a, cap, stream); break;
+      }
+      return hipGetLastError();
+    }
+  }
+  const uint8_t* sp = (const uint8_t*)src;
+  uint8_t* dp = (uint8_t*)dst;
+  switch (granule(sl, dl, (uint64_t)(uintptr_t)src,
+                  (uint64_t)(uintptr_t)dst)) {
+    case 16: launch_nd<16>(sp, sl, dp, dl, bytes, cap, stream); break;
+    case 8: launch_nd<8>(sp, sl, dp, dl, bytes, cap, stream); break;
+    case 4: launch_nd<4>(sp, sl, dp, dl, bytes, cap, stream); break;
+    case 2: launch_nd<2>(sp, sl, dp, dl, bytes, cap, stream); break;
+    default: launch_nd<1>(sp, sl, dp, dl, bytes, cap, stream); break;
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_copy_nd(void* dst, const Layout& dl, const void* src,
+                          const Layout& sl, uint64_t bytes,
+                          hipStream_t stream) {
+  return launch_copy_nd_tuned(dst, dl, src, sl, bytes, stream,
+                              default_copy_tuning(), CopyNdPath::Auto);
 }
 
 }  // namespace sw

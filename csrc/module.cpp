@@ -34,8 +34,13 @@ static BufferRef parse_buffer(py::handle obj, bool writable) {
     size_t n = 1;
     for (auto d : shape) n *= d.cast<size_t>();
     uint64_t rows = 0, row_bytes = 0, row_stride = 0;
+    Layout nd{};
     if (cai.contains("strides") && !cai["strides"].is_none()) {
       py::tuple strides = cai["strides"].cast<py::tuple>();
+      for (auto st : strides)
+        if (st.cast<int64_t>() < 0)
+          throw std::invalid_argument(
+              "N-D layout limit: negative strides are not supported");
       size_t expect = itemsize;
       bool contiguous = true;
       for (ssize_t i = (ssize_t)shape.size() - 1; i >= 0; --i) {
@@ -45,24 +50,39 @@ static BufferRef parse_buffer(py::handle obj, bool writable) {
       if (!contiguous) {
         // 2D row-strided layout is supported natively (pack/unpack in the
         // pull kernel): last dim dense, leading dim strided.
-        if (shape.size() == 2 &&
-            strides[1].cast<size_t>() == itemsize) {
+        if (shape.size() == 2 && strides[1].cast<size_t>() == itemsize &&
+            strides[0].cast<uint64_t>() >=
+                shape[1].cast<uint64_t>() * itemsize) {
           rows = shape[0].cast<uint64_t>();
           row_bytes = shape[1].cast<uint64_t>() * itemsize;
           row_stride = strides[0].cast<uint64_t>();
-          if (row_stride < row_bytes)
-            throw std::invalid_argument(
-                "overlapping strided device buffer is not supported");
-        } else {
-          throw std::invalid_argument(
-              "device buffer must be contiguous or 2D row-strided "
-              "(last dim dense) for zero-copy messaging");
+        } else if (n > 0) {
+          // Any other view: normalise it. What comes out as contiguous or
+          // as rows over a dense run keeps the fields (and kernels) above;
+          // the rest travels as an N-D layout.
+          std::vector<uint64_t> sh;
+          std::vector<int64_t> st;
+          for (size_t i = 0; i < shape.size(); i++) {
+            sh.push_back(shape[i].cast<uint64_t>());
+            st.push_back(strides[i].cast<int64_t>());
+          }
+          Layout l = normalize(sh.data(), st.data(), sh.size(), itemsize);
+          if (l.ndim == 1 && l.stride[0] >= (int64_t)l.unit) {
+            rows = l.shape[0];
+            row_bytes = l.unit;
+            row_stride = (uint64_t)l.stride[0];
+          } else if (l.ndim > 0) {
+            if (writable) check_no_overlap(l);
+            nd = l;
+          }
         }
       }
     }
     ref.ptr = (uint8_t*)ptr;
     ref.size = n * itemsize;
-    if (rows > 1) {
+    if (nd.ndim > 0) {
+      ref.nd = nd;
+    } else if (rows > 1) {
       ref.rows = rows;
       ref.row_bytes = row_bytes;
       ref.stride = row_stride;
@@ -83,6 +103,42 @@ static BufferRef parse_buffer(py::handle obj, bool writable) {
   ref.device = -1;
   PyBuffer_Release(&view);  // the keepalive object pins the memory
   return ref;
+}
+
+// (unit, [(extent, stride_bytes), ...]): a Layout as the test hooks see it.
+using Plan = std::pair<uint64_t, std::vector<std::pair<uint64_t, int64_t>>>;
+
+static Plan plan_of(const Layout& l) {
+  Plan p;
+  p.first = l.unit;
+  for (uint32_t d = 0; d < l.ndim; d++)
+    p.second.emplace_back(l.shape[d], l.stride[d]);
+  return p;
+}
+
+static Layout layout_of(const Plan& p) {
+  if (p.second.size() > kMaxDims)
+    throw std::invalid_argument("N-D layout limit: too many dimensions");
+  if (p.first > UINT32_MAX)
+    throw std::invalid_argument("N-D layout limit: unit of 4 GiB or more");
+  Layout l{};
+  l.ndim = (uint32_t)p.second.size();
+  l.unit = (uint32_t)p.first;
+  for (uint32_t d = 0; d < l.ndim; d++) {
+    l.shape[d] = p.second[d].first;
+    l.stride[d] = p.second[d].second;
+  }
+  return l;
+}
+
+static Layout layout_from(const std::vector<uint64_t>& shape,
+                          const std::vector<int64_t>& strides,
+                          uint64_t itemsize, bool writable) {
+  if (shape.size() != strides.size())
+    throw std::invalid_argument("shape and strides differ in length");
+  Layout l = normalize(shape.data(), strides.data(), shape.size(), itemsize);
+  if (writable) check_no_overlap(l);
+  return l;
 }
 
 struct PyServer {
@@ -377,6 +433,70 @@ PYBIND11_MODULE(_core, m) {
           if (!ok) throw std::runtime_error("copy_multi_sync: " + err);
         },
         py::arg("descs"), py::arg("device"));
+  // N-D layouts (layout.hpp). The two _plan_* hooks are host-only and work
+  // without a GPU. A plan is (unit, [(extent, stride_bytes), ...]), outermost
+  // dimension first; an empty list means contiguous.
+  m.def("_plan_layout",
+        [](const std::vector<uint64_t>& shape,
+           const std::vector<int64_t>& strides, uint64_t itemsize,
+           bool writable) {
+          return plan_of(layout_from(shape, strides, itemsize, writable));
+        },
+        py::arg("shape"), py::arg("strides_bytes"), py::arg("itemsize"),
+        py::arg("writable") = false);
+  m.def("_plan_granule",
+        [](const Plan& src, const Plan& dst, uint64_t src_ptr,
+           uint64_t dst_ptr) {
+          return granule(layout_of(src), layout_of(dst), src_ptr, dst_ptr);
+        },
+        py::arg("src_plan"), py::arg("dst_plan"), py::arg("src_ptr"),
+        py::arg("dst_ptr"));
+  m.def("_copy_nd_sync",
+        [](uintptr_t dst, const std::vector<uint64_t>& dst_shape,
+           const std::vector<int64_t>& dst_strides, uintptr_t src,
+           const std::vector<uint64_t>& src_shape,
+           const std::vector<int64_t>& src_strides, uint64_t itemsize,
+           int device, size_t block_cap, const std::string& path) {
+          CopyNdPath p;
+          if (path == "auto") p = CopyNdPath::Auto;
+          else if (path == "generic") p = CopyNdPath::Generic;
+          else if (path == "tiled") p = CopyNdPath::Tiled;
+          else throw py::value_error("copy_nd_sync: path must be auto, "
+                                     "generic or tiled");
+          uint64_t dbytes = itemsize, sbytes = itemsize;
+          for (uint64_t e : dst_shape) dbytes *= e;
+          for (uint64_t e : src_shape) sbytes *= e;
+          if (dbytes != sbytes)
+            throw py::value_error("copy_nd_sync: source holds " +
+                                  std::to_string(sbytes) +
+                                  " B, destination " + std::to_string(dbytes));
+          Layout dl = layout_from(dst_shape, dst_strides, itemsize, true);
+          Layout sl = layout_from(src_shape, src_strides, itemsize, false);
+          std::string err;
+          bool ok, ineligible = false;
+          {
+            py::gil_scoped_release rel;
+            ok = gpu::copy_nd_sync((void*)dst, dl, (const void*)src, sl,
+                                   sbytes, device, block_cap, p, &ineligible,
+                                   &err);
+          }
+          if (ineligible) throw py::value_error("copy_nd_sync: " + err);
+          if (!ok) throw std::runtime_error("copy_nd_sync: " + err);
+        },
+        py::arg("dst"), py::arg("dst_shape"), py::arg("dst_strides"),
+        py::arg("src"), py::arg("src_shape"), py::arg("src_strides"),
+        py::arg("itemsize"), py::arg("device"), py::arg("block_cap") = 0,
+        py::arg("path") = "auto");
+  // Tile extents of k_copy_nd_tile: element bytes -> (T_A, T_B) elements.
+  {
+    py::dict tiles;
+    for (int e : {1, 2, 4, 8, 16}) {
+      int t = gpu::copy_nd_tile_extent(e);
+      tiles[py::int_(e)] = py::make_tuple(t, t);
+    }
+    m.attr("_ND_TILE") = tiles;
+    m.attr("_ND_MAX_DIMS") = kMaxDims;
+  }
   m.def("_copy_tuning", [] {
     CopyTuning t = gpu::copy_tuning();
     py::dict d;

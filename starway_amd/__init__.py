@@ -101,6 +101,10 @@ class _CudaShim:
     the tensor via a strong reference (the core keeps this shim alive as the
     op's keepalive). Used instead of the tensor's own CAI so behavior is
     identical across torch builds.
+
+    Any view is accepted. The message is the bytes of ``t.contiguous()``
+    (logical row-major order); a non-contiguous view is packed or unpacked
+    inside the copy kernels, never staged through ``.contiguous()``.
     """
 
     __slots__ = ("_t", "__cuda_array_interface__")
@@ -128,15 +132,29 @@ class _CudaShim:
                 "version": 2,
             }
         else:
-            raise ValueError(
-                "device message buffers must be contiguous or 2D row-strided "
-                "(call .contiguous() first)"
-            )
+            # Any other view (transpose, permute, N-D slice, stepped slice,
+            # expand): the real geometry in bytes; the core normalises it
+            # and packs/unpacks inside the N-D copy kernels.
+            self.__cuda_array_interface__ = {
+                "data": (t.data_ptr(), False),
+                "shape": tuple(t.shape),
+                "typestr": f"|V{es}",
+                "strides": tuple(s * es for s in t.stride()),
+                "version": 2,
+            }
         self._t = t
         try:
             t._sw_cai = self.__cuda_array_interface__
+            t._sw_key = _layout_key(t)
         except Exception:
             pass  # tensor subclass without attribute support
+
+
+def _layout_key(t) -> tuple:
+    """What the cached interface dict depends on. An in-place t_() or
+    as_strided_() keeps the tensor object and its data pointer but changes
+    the layout, so the pointer alone does not validate the cache."""
+    return (t.data_ptr(), tuple(t.shape), t.stride(), t.element_size())
 
 
 def _norm_buffer(buf: Any) -> Any:
@@ -154,7 +172,7 @@ def _norm_buffer(buf: Any) -> Any:
             # it doubles as the op's keepalive (a cached shim would form a
             # tensor<->shim cycle and pin GPU memory on the GC).
             cai = getattr(buf, "_sw_cai", None)
-            if cai is None or cai["data"][0] != buf.data_ptr():
+            if cai is None or getattr(buf, "_sw_key", None) != _layout_key(buf):
                 return _CudaShim(buf)
             shim = _CudaShim.__new__(_CudaShim)
             shim.__cuda_array_interface__ = cai

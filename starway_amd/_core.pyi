@@ -108,4 +108,40 @@ def _copy_multi_sync(
 ) -> None: ...
 def _copy_tuning() -> dict[str, int]: ...
 
+# N-D layouts (csrc/layout.hpp). A plan is (unit, [(extent, stride_bytes),
+# ...]): `unit` bytes of dense innermost run, then the dimensions outside
+# it, outermost first; an empty list means contiguous. Message byte m lives
+# at offset (m % unit) + sum(idx_d * stride_d), idx peeled from m // unit
+# innermost first.
+_Plan = tuple[int, list[tuple[int, int]]]
+
+def _plan_layout(
+    shape: list[int], strides_bytes: list[int], itemsize: int,
+    writable: bool = False,
+) -> _Plan:
+    """Normalise a view: drop size-1 dimensions, merge neighbours, fold a
+    dense innermost dimension into `unit`. ValueError for negative strides,
+    more than _ND_MAX_DIMS remaining dimensions and, with writable=True,
+    overlapping elements. Host only: works without a GPU."""
+
+def _plan_granule(
+    src_plan: _Plan, dst_plan: _Plan, src_ptr: int, dst_ptr: int
+) -> int:
+    """Largest power of two <= 16 dividing both units, every stride and
+    both addresses: the access width k_copy_nd runs with. Host only."""
+
+def _copy_nd_sync(
+    dst: int, dst_shape: list[int], dst_strides: list[int],
+    src: int, src_shape: list[int], src_strides: list[int],
+    itemsize: int, device: int, block_cap: int = 0, path: str = "auto",
+) -> None:
+    """Run the N-D copy kernels synchronously on raw device pointers
+    (strides in bytes). path: "auto" (the production dispatch), "generic"
+    (k_copy_nd) or "tiled" (k_copy_nd_tile; ValueError when the pair is not
+    in the transpose family)."""
+
+# k_copy_nd_tile tile extents: element bytes -> (T_A, T_B) in elements.
+_ND_TILE: dict[int, tuple[int, int]]
+_ND_MAX_DIMS: int
+
 __version__: str
