@@ -782,10 +782,12 @@ void unpack_free(void* ticket);
 
 // Doorbell: pre-armed bounded wait for the next sequence number, copying
 // into dst on a tag match. arm_poll: 0 running / 1 copied / 2 nomatch /
-// 3 canceled / 4 expired.
+// 3 canceled / 4 expired. spin_iters bounds the wait; 0 means the process
+// default (STARWAY_ARM_SPIN). A kernel that finds its cancel word set when
+// it starts reports 3 and never reads the slot or writes dst.
 void* arm_recv(const InboxInfo& mine, uint64_t expect_seq, uint64_t tag,
                uint64_t mask, uint8_t* dst, uint64_t max_size, int lane,
-               std::string* err);
+               unsigned spin_iters, std::string* err);
 int arm_poll(void* ticket, uint64_t* size_out);
 void arm_cancel(void* ticket);
 void arm_free(void* ticket);
@@ -819,6 +821,30 @@ struct CopyDesc {
 };
 bool copy_multi_sync(const CopyDesc* descs, int n, int device,
                      std::string* err);
+// Test hooks for the inbox kernels (smallmsg.hip). They drive the kernels
+// through the host functions above (same-process push, lane 0) and wait
+// under a host deadline; none of them launches a kernel of its own.
+bool inbox_ring_read(const InboxInfo& ring, uint8_t* out, std::string* err);
+bool inbox_ring_write(const InboxInfo& ring, uint64_t offset,
+                      const uint8_t* data, uint64_t n, std::string* err);
+// One k_inbox_push launch, polled to completion, ticket freed.
+bool inbox_push_sync(const InboxInfo& ring, const PushMsg* msgs, int n,
+                     int run_device, std::string* err);
+// One k_inbox_unpack launch. status[i] is the kernel's result word (1 ok /
+// 2 payload never arrived); bounce[i] holds the pinned staging bytes of a
+// message whose dst was null and is empty otherwise.
+bool inbox_unpack_sync(const InboxInfo& ring, const UnpackMsg* msgs, int n,
+                       int* status, std::vector<uint8_t>* bounce,
+                       std::string* err);
+// arm_recv, with the cancel word optionally set BEFORE the launch is
+// enqueued (the kernel then starts canceled, whatever the queue does).
+void* arm_begin(const InboxInfo& ring, uint64_t expect_seq, uint64_t tag,
+                uint64_t mask, uint8_t* dst, uint64_t max_size,
+                unsigned spin_iters, bool precancel, std::string* err);
+// Wait for the kernel's verdict, then free the ticket. Past the deadline:
+// cancel, wait 100 ms, and leak the cell if the kernel still has not
+// reported (false; the ticket is gone either way).
+bool arm_end(void* ticket, int* status, uint64_t* size, std::string* err);
 // Stats for evaluate_perf / transports introspection. Values come from a
 // cached on-box copy microbenchmark (~/.cache/starway/perf.cal) with
 // round-1 measurements as analytic fallback.

@@ -444,7 +444,7 @@ void Engine::try_arm() {
   std::string err;
   void* t = gpu::arm_recv(target->inbox_l, target->inbox_seen_seq + 1,
                           r->tag, r->tag_mask, r->buf.ptr, r->buf.size,
-                          engine_lane_, &err);
+                          engine_lane_, /*spin_iters=*/0, &err);
   if (!t) {
     SW_DBG("arm failed: %s", err.c_str());
     return;

@@ -90,13 +90,41 @@ int unpack_poll(void*, int, std::string*) { return -1; }
 const uint8_t* unpack_bounce(void*, int) { return nullptr; }
 void unpack_free(void*) {}
 void* arm_recv(const InboxInfo&, uint64_t, uint64_t, uint64_t, uint8_t*,
-               uint64_t, int, std::string* err) {
+               uint64_t, int, unsigned, std::string* err) {
   *err = "no GPU (sanitizer stub)";
   return nullptr;
 }
 int arm_poll(void*, uint64_t*) { return 4; }
 void arm_cancel(void*) {}
 void arm_free(void*) {}
+bool inbox_ring_read(const InboxInfo&, uint8_t*, std::string* err) {
+  *err = "no GPU (sanitizer stub)";
+  return false;
+}
+bool inbox_ring_write(const InboxInfo&, uint64_t, const uint8_t*, uint64_t,
+                      std::string* err) {
+  *err = "no GPU (sanitizer stub)";
+  return false;
+}
+bool inbox_push_sync(const InboxInfo&, const PushMsg*, int, int,
+                     std::string* err) {
+  *err = "no GPU (sanitizer stub)";
+  return false;
+}
+bool inbox_unpack_sync(const InboxInfo&, const UnpackMsg*, int, int*,
+                       std::vector<uint8_t>*, std::string* err) {
+  *err = "no GPU (sanitizer stub)";
+  return false;
+}
+void* arm_begin(const InboxInfo&, uint64_t, uint64_t, uint64_t, uint8_t*,
+                uint64_t, unsigned, bool, std::string* err) {
+  *err = "no GPU (sanitizer stub)";
+  return nullptr;
+}
+bool arm_end(void*, int*, uint64_t*, std::string* err) {
+  *err = "no GPU (sanitizer stub)";
+  return false;
+}
 
 }  // namespace gpu
 }  // namespace sw

@@ -141,6 +141,45 @@ static Layout layout_from(const std::vector<uint64_t>& shape,
   return l;
 }
 
+// Inbox test hooks: a ring is either live (device memory from
+// inbox_create) or detached (geometry only, built from Python: it lets the
+// argument checks run without a device and is refused by everything that
+// would touch one).
+struct PyInboxRing {
+  gpu::InboxInfo info;
+  bool live = false;
+  uint32_t payload_max() const {
+    return info.slot_bytes - gpu::kInboxHdrBytes;
+  }
+};
+
+struct PyArmTicket {
+  void* ticket = nullptr;
+};
+
+static void need_live(const PyInboxRing& r, const char* what) {
+  if (!r.live)
+    throw std::runtime_error(std::string(what) +
+                             ": ring has no device memory (detached or "
+                             "destroyed)");
+}
+
+static void check_inbox_batch(const char* what, size_t n) {
+  if (n < 1 || n > 32)
+    throw py::value_error(std::string(what) + ": need 1..32 descriptors");
+}
+
+static void check_inbox_msg(const char* what, const PyInboxRing& r,
+                            uint64_t seq, uint64_t size) {
+  if (seq == 0)
+    throw py::value_error(std::string(what) +
+                          ": seq 0 is the empty-slot sentinel");
+  if (size > r.payload_max())
+    throw py::value_error(std::string(what) + ": size " +
+                          std::to_string(size) + " exceeds payload_max " +
+                          std::to_string(r.payload_max()));
+}
+
 struct PyServer {
   Engine engine{Engine::ServerMode};
   explicit PyServer(Context&) {
@@ -504,6 +543,198 @@ PYBIND11_MODULE(_core, m) {
     d["nt_threshold"] = t.nt_threshold;
     d["nt_unroll"] = t.nt_unroll;
     return d;
+  });
+  // Test hooks for the small-message kernels (smallmsg.hip). They go
+  // through the host functions the engine uses (inbox_create, same-process
+  // inbox_push, inbox_unpack, arm_recv's two halves, arm_poll / arm_cancel
+  // / arm_free / arm_leak); every wait has a ~2 s host deadline.
+  py::class_<PyInboxRing>(m, "_InboxRing")
+      .def(py::init([](uint32_t slots, uint32_t slot_bytes) {
+             if (slots == 0 || slot_bytes < gpu::kInboxHdrBytes)
+               throw py::value_error("_InboxRing: bad geometry");
+             PyInboxRing r;
+             r.info.slots = slots;
+             r.info.slot_bytes = slot_bytes;
+             return r;
+           }),
+           py::arg("slots"), py::arg("slot_bytes"))
+      .def_property_readonly("slots",
+                             [](const PyInboxRing& r) { return r.info.slots; })
+      .def_property_readonly(
+          "slot_bytes", [](const PyInboxRing& r) { return r.info.slot_bytes; })
+      .def_property_readonly(
+          "hdr_bytes", [](const PyInboxRing&) { return gpu::kInboxHdrBytes; })
+      .def_property_readonly(
+          "payload_max", [](const PyInboxRing& r) { return r.payload_max(); })
+      .def_property_readonly("device",
+                             [](const PyInboxRing& r) { return r.info.device; })
+      .def_property_readonly("live",
+                             [](const PyInboxRing& r) { return r.live; });
+  py::class_<PyArmTicket>(m, "_InboxArmTicket");
+  m.def("_inbox_ring_create",
+        [](int device) {
+          PyInboxRing r;
+          std::string err;
+          bool ok;
+          {
+            py::gil_scoped_release rel;
+            ok = gpu::inbox_create(&r.info, device, &err);
+          }
+          if (!ok) throw std::runtime_error("inbox_ring_create: " + err);
+          r.live = true;
+          return r;
+        },
+        py::arg("device"));
+  m.def("_inbox_ring_destroy", [](PyInboxRing& r) {
+    need_live(r, "inbox_ring_destroy");
+    r.live = false;
+    py::gil_scoped_release rel;
+    gpu::inbox_destroy(r.info);
+  });
+  m.def("_inbox_ring_read", [](const PyInboxRing& r) {
+    need_live(r, "inbox_ring_read");
+    std::string out((size_t)r.info.slots * r.info.slot_bytes, '\0');
+    std::string err;
+    bool ok;
+    {
+      py::gil_scoped_release rel;
+      ok = gpu::inbox_ring_read(r.info, (uint8_t*)out.data(), &err);
+    }
+    if (!ok) throw std::runtime_error("inbox_ring_read: " + err);
+    return py::bytes(out);
+  });
+  m.def("_inbox_ring_write",
+        [](const PyInboxRing& r, uint64_t offset, py::buffer data) {
+          py::buffer_info bi = data.request();
+          if (!PyBuffer_IsContiguous(bi.view(), 'C'))
+            throw py::value_error("inbox_ring_write: data not contiguous");
+          uint64_t n = (uint64_t)bi.size * (uint64_t)bi.itemsize;
+          uint64_t total = (uint64_t)r.info.slots * r.info.slot_bytes;
+          if (offset > total || n > total - offset)
+            throw py::value_error("inbox_ring_write: out of range");
+          need_live(r, "inbox_ring_write");
+          std::string err;
+          bool ok;
+          {
+            py::gil_scoped_release rel;
+            ok = gpu::inbox_ring_write(r.info, offset,
+                                       (const uint8_t*)bi.ptr, n, &err);
+          }
+          if (!ok) throw std::runtime_error("inbox_ring_write: " + err);
+        },
+        py::arg("ring"), py::arg("offset"), py::arg("data"));
+  // msgs: list of (src_ptr, size, seq, tag); one k_inbox_push launch.
+  m.def("_inbox_push_sync",
+        [](const PyInboxRing& r,
+           const std::vector<std::tuple<uintptr_t, uint64_t, uint64_t,
+                                        uint64_t>>& msgs,
+           int run_device) {
+          check_inbox_batch("inbox_push_sync", msgs.size());
+          gpu::PushMsg pm[32];
+          for (size_t i = 0; i < msgs.size(); i++) {
+            auto [src, size, seq, tag] = msgs[i];
+            check_inbox_msg("inbox_push_sync", r, seq, size);
+            pm[i] = gpu::PushMsg{(const uint8_t*)src, (uint32_t)size, seq, tag};
+          }
+          need_live(r, "inbox_push_sync");
+          std::string err;
+          bool ok;
+          {
+            py::gil_scoped_release rel;
+            ok = gpu::inbox_push_sync(r.info, pm, (int)msgs.size(),
+                                      run_device, &err);
+          }
+          if (!ok) throw std::runtime_error("inbox_push_sync: " + err);
+        },
+        py::arg("ring"), py::arg("msgs"), py::arg("run_device"));
+  // msgs: list of (seq, size, dst_ptr or 0); one k_inbox_unpack launch.
+  // Returns [(status, bounce bytes or None)]: status 1 delivered, 2 the
+  // payload never arrived within the kernel's spin bound.
+  m.def("_inbox_unpack_sync",
+        [](const PyInboxRing& r,
+           const std::vector<std::tuple<uint64_t, uint64_t, uintptr_t>>&
+               msgs) {
+          check_inbox_batch("inbox_unpack_sync", msgs.size());
+          gpu::UnpackMsg um[32];
+          for (size_t i = 0; i < msgs.size(); i++) {
+            auto [seq, size, dst] = msgs[i];
+            check_inbox_msg("inbox_unpack_sync", r, seq, size);
+            um[i] = gpu::UnpackMsg{seq, (uint32_t)size, (uint8_t*)dst};
+          }
+          need_live(r, "inbox_unpack_sync");
+          int status[32];
+          std::vector<uint8_t> bounce[32];
+          std::string err;
+          bool ok;
+          {
+            py::gil_scoped_release rel;
+            ok = gpu::inbox_unpack_sync(r.info, um, (int)msgs.size(), status,
+                                        bounce, &err);
+          }
+          if (!ok) throw std::runtime_error("inbox_unpack_sync: " + err);
+          py::list out;
+          for (size_t i = 0; i < msgs.size(); i++) {
+            py::object b = py::none();
+            if (!um[i].dst)
+              b = py::bytes((const char*)bounce[i].data(), bounce[i].size());
+            out.append(py::make_tuple(status[i], b));
+          }
+          return out;
+        },
+        py::arg("ring"), py::arg("msgs"));
+  m.def("_inbox_arm_begin",
+        [](const PyInboxRing& r, uint64_t expect_seq, uint64_t tag,
+           uint64_t mask, uintptr_t dst, uint64_t max_size,
+           unsigned spin_iters, bool precancel) {
+          // max_size is the buffer's capacity, not a message size: only
+          // what is pushed is bounded by the slot.
+          check_inbox_msg("inbox_arm_begin", r, expect_seq, 0);
+          need_live(r, "inbox_arm_begin");
+          std::string err;
+          PyArmTicket t;
+          {
+            py::gil_scoped_release rel;
+            t.ticket = gpu::arm_begin(r.info, expect_seq, tag, mask,
+                                      (uint8_t*)dst, max_size, spin_iters,
+                                      precancel, &err);
+          }
+          if (!t.ticket) throw std::runtime_error("inbox_arm_begin: " + err);
+          return t;
+        },
+        py::arg("ring"), py::arg("expect_seq"), py::arg("tag"),
+        py::arg("mask"), py::arg("dst"), py::arg("max_size"),
+        py::arg("spin_iters") = 0, py::arg("precancel") = false);
+  auto need_ticket = [](const PyArmTicket& t, const char* what) {
+    if (!t.ticket)
+      throw std::runtime_error(std::string(what) + ": ticket already ended");
+  };
+  // (status, size): 0 running / 1 copied / 2 nomatch / 3 canceled /
+  // 4 expired; size is the message's, non-zero with status 1 only.
+  m.def("_inbox_arm_poll", [need_ticket](const PyArmTicket& t) {
+    need_ticket(t, "inbox_arm_poll");
+    uint64_t size = 0;
+    int st = gpu::arm_poll(t.ticket, &size);
+    return py::make_tuple(st, size);
+  });
+  m.def("_inbox_arm_cancel", [need_ticket](const PyArmTicket& t) {
+    need_ticket(t, "inbox_arm_cancel");
+    gpu::arm_cancel(t.ticket);
+  });
+  // Waits for a verdict, frees the ticket, returns (status, size).
+  m.def("_inbox_arm_end", [need_ticket](PyArmTicket& t) {
+    need_ticket(t, "inbox_arm_end");
+    void* ticket = t.ticket;
+    t.ticket = nullptr;  // freed or leaked below, never reusable
+    int st = 0;
+    uint64_t size = 0;
+    std::string err;
+    bool ok;
+    {
+      py::gil_scoped_release rel;
+      ok = gpu::arm_end(ticket, &st, &size, &err);
+    }
+    if (!ok) throw std::runtime_error("inbox_arm_end: " + err);
+    return py::make_tuple(st, size);
   });
   m.attr("__version__") = "0.1.0";
 }

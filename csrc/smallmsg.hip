@@ -38,8 +38,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <map>
 #include <mutex>
+#include <thread>
 #include <tuple>
 #include <vector>
 
@@ -168,11 +170,21 @@ struct ArmArgs {
 // 4 expired. The kernel only CONSUMES a message whose header matches its
 // armed (tag, mask) and fits the buffer; anything else is left in the slot
 // for the engine's ordinary matching path.
+//
+// Cancel before start: the host may give up on a kernel that has not begun
+// (launch-queue backlog) and hand dst to another delivery path. The cancel
+// word is therefore read once on entry, before the slot: a kernel that
+// starts canceled reports 3 and touches neither the slot nor dst, even if
+// its message is already published. Inside the loop the word is polled
+// every 64th iteration only, after the slot.
 __global__ __launch_bounds__(256) void k_inbox_wait(ArmArgs a) {
   __shared__ unsigned long long st;
   if (threadIdx.x == 0) {
     unsigned long long status = 4;  // expired unless something happens
-    for (unsigned it = 0; it < a.spin_iters; ++it) {
+    bool canceled = __hip_atomic_load(a.cancel, __ATOMIC_RELAXED,
+                                      __HIP_MEMORY_SCOPE_SYSTEM) != 0;
+    if (canceled) status = 3;
+    for (unsigned it = 0; !canceled && it < a.spin_iters; ++it) {
       unsigned long long s = __hip_atomic_load(
           (const unsigned long long*)a.slot, __ATOMIC_RELAXED,
           __HIP_MEMORY_SCOPE_SYSTEM);
@@ -578,9 +590,13 @@ struct ArmTicket {
   int device = -1;
 };
 
-void* arm_recv(const InboxInfo& mine, uint64_t expect_seq, uint64_t tag,
-               uint64_t mask, uint8_t* dst, uint64_t max_size, int lane,
-               std::string* err) {
+// arm_recv in two steps, so a caller can set the cancel word between them:
+// arm_prepare takes the pinned cell and fills the kernel arguments,
+// arm_launch enqueues the wait kernel (and frees the ticket if that fails).
+static ArmTicket* arm_prepare(const InboxInfo& mine, uint64_t expect_seq,
+                              uint64_t tag, uint64_t mask, uint8_t* dst,
+                              uint64_t max_size, unsigned spin_iters,
+                              ArmArgs* a, std::string* err) {
   std::lock_guard<std::mutex> lk(sm_mu);
   init_pools();
   uint8_t* cell = g_flag_pool.get();
@@ -594,30 +610,45 @@ void* arm_recv(const InboxInfo& mine, uint64_t expect_seq, uint64_t tag,
   t->device = mine.device;
   static const unsigned spin =
       (unsigned)env_u64("STARWAY_ARM_SPIN", 8000);  // ~1 ms bound
-  ArmArgs a;
-  a.slot = (const uint8_t*)(uintptr_t)mine.base +
-           (expect_seq % mine.slots) * mine.slot_bytes;
-  a.expect_seq = expect_seq;
-  a.tag = tag;
-  a.mask = mask;
-  a.dst = dst;
-  a.max_size = max_size;
-  a.result = t->result;
-  a.cancel = t->cancel;
-  a.spin_iters = spin;
+  a->slot = (const uint8_t*)(uintptr_t)mine.base +
+            (expect_seq % mine.slots) * mine.slot_bytes;
+  a->expect_seq = expect_seq;
+  a->tag = tag;
+  a->mask = mask;
+  a->dst = dst;
+  a->max_size = max_size;
+  a->result = t->result;
+  a->cancel = t->cancel;
+  a->spin_iters = spin_iters ? spin_iters : spin;
+  return t;
+}
+
+static bool arm_launch(ArmTicket* t, const ArmArgs& a, int lane,
+                       std::string* err) {
+  std::lock_guard<std::mutex> lk(sm_mu);
   int prev;
   hipGetDevice(&prev);
-  hipSetDevice(mine.device);
-  hipStream_t stream = sm_stream(mine.device, SmStream::Wait, lane);
+  hipSetDevice(t->device);
+  hipStream_t stream = sm_stream(t->device, SmStream::Wait, lane);
   hipLaunchKernelGGL(k_inbox_wait, dim3(1), dim3(256), 0, stream, a);
   hipError_t e = hipGetLastError();
   hipSetDevice(prev);
   if (e != hipSuccess) {
     *err = std::string("arm: ") + hipGetErrorString(e);
-    g_flag_pool.put(cell);
+    g_flag_pool.put((uint8_t*)t->result);
     delete t;
-    return nullptr;
+    return false;
   }
+  return true;
+}
+
+void* arm_recv(const InboxInfo& mine, uint64_t expect_seq, uint64_t tag,
+               uint64_t mask, uint8_t* dst, uint64_t max_size, int lane,
+               unsigned spin_iters, std::string* err) {
+  ArmArgs a;
+  ArmTicket* t = arm_prepare(mine, expect_seq, tag, mask, dst, max_size,
+                             spin_iters, &a, err);
+  if (!t || !arm_launch(t, a, lane, err)) return nullptr;
   return t;
 }
 
@@ -645,6 +676,129 @@ void arm_free(void* ticket) {
 // its result later: the pinned cell must NOT return to the pool. Leaks one
 // 64 B cell — correctness over thrift.
 void arm_leak(void* ticket) { delete (ArmTicket*)ticket; }
+
+// ---------------------------------------------------------------------------
+// test hooks: the kernels above, reached through the host functions above
+// ---------------------------------------------------------------------------
+
+// Poll `done` until it holds or `ms` have passed; true when it held.
+template <class F>
+static bool hook_wait(long ms, F done) {
+  auto deadline =
+      std::chrono::steady_clock::now() + std::chrono::milliseconds(ms);
+  for (;;) {
+    if (done()) return true;
+    if (std::chrono::steady_clock::now() >= deadline) return done();
+    std::this_thread::yield();
+  }
+}
+
+constexpr long kHookDeadlineMs = 2000;
+
+static bool ring_copy(const InboxInfo& ring, void* dst, const void* src,
+                      size_t n, hipMemcpyKind kind, const char* what,
+                      std::string* err) {
+  int prev = 0;
+  hipGetDevice(&prev);
+  hipError_t e = hipSetDevice(ring.device);
+  if (e == hipSuccess) e = hipMemcpy(dst, src, n, kind);
+  hipSetDevice(prev);
+  if (e != hipSuccess) {
+    *err = std::string(what) + ": " + hipGetErrorString(e);
+    return false;
+  }
+  return true;
+}
+
+bool inbox_ring_read(const InboxInfo& ring, uint8_t* out, std::string* err) {
+  return ring_copy(ring, out, (const void*)(uintptr_t)ring.base,
+                   (size_t)ring.slots * ring.slot_bytes,
+                   hipMemcpyDeviceToHost, "ring read", err);
+}
+
+bool inbox_ring_write(const InboxInfo& ring, uint64_t offset,
+                      const uint8_t* data, uint64_t n, std::string* err) {
+  uint64_t total = (uint64_t)ring.slots * ring.slot_bytes;
+  if (offset > total || n > total - offset) {
+    *err = "ring write: out of range";
+    return false;
+  }
+  if (n == 0) return true;
+  return ring_copy(ring, (uint8_t*)(uintptr_t)ring.base + offset, data, n,
+                   hipMemcpyHostToDevice, "ring write", err);
+}
+
+bool inbox_push_sync(const InboxInfo& ring, const PushMsg* msgs, int n,
+                     int run_device, std::string* err) {
+  void* t = inbox_push(ring, /*same_proc=*/true, run_device, msgs, n,
+                       /*lane=*/0, err);
+  if (!t) return false;
+  int r = 0;
+  hook_wait(kHookDeadlineMs, [&] { return (r = push_poll(t, err)) != 0; });
+  // The ticket holds an event only; the kernel never writes through it.
+  push_free(t);
+  if (r == 0) *err = "push did not complete within the deadline";
+  return r > 0;
+}
+
+bool inbox_unpack_sync(const InboxInfo& ring, const UnpackMsg* msgs, int n,
+                       int* status, std::vector<uint8_t>* bounce,
+                       std::string* err) {
+  void* t = inbox_unpack(ring, msgs, n, /*lane=*/0, err);
+  if (!t) return false;
+  bool all = hook_wait(kHookDeadlineMs, [&] {
+    for (int i = 0; i < n; i++) {
+      std::string ignored;
+      if (unpack_poll(t, i, &ignored) == 0) return false;
+    }
+    return true;
+  });
+  if (!all) {
+    // The kernel may still write its result words and bounces: the ticket
+    // and its pinned cells are leaked, never returned to the pool.
+    *err = "unpack did not complete within the deadline";
+    return false;
+  }
+  for (int i = 0; i < n; i++) {
+    std::string ignored;
+    status[i] = unpack_poll(t, i, &ignored) > 0 ? 1 : 2;
+    bounce[i].clear();
+    if (const uint8_t* b = unpack_bounce(t, i))
+      bounce[i].assign(b, b + msgs[i].size);
+  }
+  unpack_free(t);
+  return true;
+}
+
+void* arm_begin(const InboxInfo& ring, uint64_t expect_seq, uint64_t tag,
+                uint64_t mask, uint8_t* dst, uint64_t max_size,
+                unsigned spin_iters, bool precancel, std::string* err) {
+  ArmArgs a;
+  ArmTicket* t = arm_prepare(ring, expect_seq, tag, mask, dst, max_size,
+                             spin_iters, &a, err);
+  if (!t) return nullptr;
+  if (precancel) arm_cancel(t);
+  if (!arm_launch(t, a, /*lane=*/0, err)) return nullptr;
+  return t;
+}
+
+bool arm_end(void* ticket, int* status, uint64_t* size, std::string* err) {
+  auto reported = [&] { return (*status = arm_poll(ticket, size)) != 0; };
+  *size = 0;
+  if (hook_wait(kHookDeadlineMs, reported)) {
+    arm_free(ticket);
+    return true;
+  }
+  arm_cancel(ticket);
+  if (hook_wait(100, reported)) {
+    arm_free(ticket);
+    *err = "wait kernel reported only after the deadline's cancel";
+    return false;
+  }
+  arm_leak(ticket);  // it may still write its result word
+  *err = "wait kernel did not report within the deadline";
+  return false;
+}
 
 }  // namespace gpu
 }  // namespace sw

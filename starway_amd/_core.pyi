@@ -144,4 +144,66 @@ def _copy_nd_sync(
 _ND_TILE: dict[int, tuple[int, int]]
 _ND_MAX_DIMS: int
 
+# Test hooks for the small-message kernels (csrc/smallmsg.hip). They call the
+# host functions the engine calls; every wait has a host deadline of ~2 s.
+# ValueError for a batch outside 1..32, a size above payload_max, seq 0 or a
+# ring write out of range -- all checked before a device is touched.
+class _InboxRing:
+    """A ring from _inbox_ring_create (live), or geometry only when built
+    here (detached: passes the argument checks, refused with RuntimeError by
+    anything that needs device memory)."""
+
+    def __init__(self, slots: int, slot_bytes: int) -> None: ...
+    @property
+    def slots(self) -> int: ...
+    @property
+    def slot_bytes(self) -> int: ...
+    @property
+    def hdr_bytes(self) -> int: ...
+    @property
+    def payload_max(self) -> int: ...
+    @property
+    def device(self) -> int: ...
+    @property
+    def live(self) -> bool: ...
+
+class _InboxArmTicket: ...
+
+def _inbox_ring_create(device: int) -> _InboxRing: ...
+def _inbox_ring_destroy(ring: _InboxRing) -> None: ...
+def _inbox_ring_read(ring: _InboxRing) -> bytes:
+    """Device-to-host copy of the whole ring."""
+
+def _inbox_ring_write(ring: _InboxRing, offset: int, data: bytes) -> None: ...
+def _inbox_push_sync(
+    ring: _InboxRing, msgs: list[tuple[int, int, int, int]], run_device: int
+) -> None:
+    """One k_inbox_push launch over (src_ptr, size, seq, tag) descriptors,
+    polled to completion."""
+
+def _inbox_unpack_sync(
+    ring: _InboxRing, msgs: list[tuple[int, int, int]]
+) -> list[tuple[int, bytes | None]]:
+    """One k_inbox_unpack launch over (seq, size, dst_ptr or 0). Per
+    message: status 1 (delivered) or 2 (payload never arrived within the
+    kernel's spin bound), and the pinned bounce's `size` bytes when dst_ptr
+    was 0, else None."""
+
+def _inbox_arm_begin(
+    ring: _InboxRing, expect_seq: int, tag: int, mask: int, dst: int,
+    max_size: int, spin_iters: int = 0, precancel: bool = False,
+) -> _InboxArmTicket:
+    """Launch k_inbox_wait. spin_iters=0 is the process default. With
+    precancel the cancel word is set before the launch is enqueued."""
+
+def _inbox_arm_poll(ticket: _InboxArmTicket) -> tuple[int, int]:
+    """(status, size): 0 running, 1 copied (`size` bytes), 2 nomatch,
+    3 canceled, 4 expired."""
+
+def _inbox_arm_cancel(ticket: _InboxArmTicket) -> None: ...
+def _inbox_arm_end(ticket: _InboxArmTicket) -> tuple[int, int]:
+    """Wait for a non-zero status, free the ticket, return (status, size).
+    RuntimeError past the deadline; the pinned cell of a kernel that still
+    has not reported is leaked, never reused."""
+
 __version__: str
