@@ -118,11 +118,16 @@ def build(verbose: bool = True, debug: bool = False) -> Path:
     bench_obj = BUILD / "copy_bench_main.o"
     if bench_src.exists():
         (REPO / "bin").mkdir(exist_ok=True)
-        if _needs_rebuild(bench_obj, bench_src, hdrs) or not bench_bin.exists():
+        kernels_obj = BUILD / "kernels_hip.o"
+        if _needs_rebuild(bench_obj, bench_src, hdrs):
             subprocess.run([HIPCC, *common, "-c", str(bench_src), "-o",
                             str(bench_obj)], check=True)
-            subprocess.run([HIPCC, str(bench_obj),
-                            str(BUILD / "kernels_hip.o"), "-o",
+        # Relink whenever either object is newer: the production route and
+        # its defaults live in kernels.hip.
+        if (not bench_bin.exists() or
+                max(bench_obj.stat().st_mtime, kernels_obj.stat().st_mtime)
+                > bench_bin.stat().st_mtime):
+            subprocess.run([HIPCC, str(bench_obj), str(kernels_obj), "-o",
                             str(bench_bin)], check=True)
     return out
 

@@ -13,14 +13,24 @@ struct CopyTuning {
   size_t nt_threshold;  // bulk bytes at/above which the non-temporal kernels
                         // run (STARWAY_NT_THRESHOLD)
   int nt_unroll;        // >= 8 selects the x8 NT kernel (STARWAY_COPY_UNROLL)
+  // Tile-contiguous streaming kernel (copy_stream.hpp). Appended, so
+  // CopyTuning{block_cap, nt_threshold, nt_unroll} leaves both at 0, which
+  // the hooks resolve to the process default.
+  size_t stream_threshold = 0;  // bulk bytes at/above which it runs
+                                // (STARWAY_STREAM_THRESHOLD)
+  size_t stream_blocks = 0;     // its grid cap (STARWAY_STREAM_BLOCKS)
 };
+
+// stream_threshold value that no message reaches: the streaming kernel off.
+constexpr size_t kStreamNever = ~(size_t)0;
 
 // Which kernel an N-D copy (launch_copy_nd_tuned) runs. Auto is what
 // production uses; the hooks force one so tests and benches reach both.
 enum class CopyNdPath : int { Auto = 0, Generic = 1, Tiled = 2 };
 
-// Environment-derived default (8192 blocks, 64 MiB, x4), read once per
-// process. Host-only: never touches the GPU.
+// Environment-derived default (8192 blocks, 64 MiB, x4; streaming kernel
+// from 64 MiB, 8192 blocks), read once per process. Host-only: never
+// touches the GPU.
 const CopyTuning& default_copy_tuning();
 
 }  // namespace sw

@@ -799,6 +799,9 @@ void synchronize_all();
 // Test/bench hooks: synchronous copy-kernel launches on the pull stream.
 // A zero field in `tuning` / a zero block_cap means the default tuning.
 CopyTuning copy_tuning();  // the default; never touches the GPU
+// Elements per lane per tile (U) of the production streaming kernel
+// (copy_stream.hpp); a compile-time constant, never touches the GPU.
+int copy_stream_unroll();
 bool copy_device_sync(void* dst, const void* src, size_t n, int device,
                       const CopyTuning& tuning, std::string* err);
 bool copy_strided_sync(void* dst, uint64_t dst_stride, const void* src,

@@ -27,8 +27,11 @@ struct MultiCopyDesc {
 };
 hipError_t launch_copy_multi(const MultiCopyDesc* descs, int n,
                              hipStream_t stream);
+// same_device: src and dst live on the GPU that runs the kernel. Only then
+// may the copy take the streaming route (see launch_copy in kernels.hip).
 hipError_t launch_copy(void* dst, const void* src, size_t bytes,
-                       hipStream_t stream);
+                       hipStream_t stream, bool same_device);
+int copy_stream_unroll();
 hipError_t launch_copy_strided(void* dst, uint64_t dst_stride,
                                const void* src, uint64_t src_stride,
                                uint64_t rows, uint64_t row_bytes,
@@ -123,6 +126,10 @@ struct Calib {
   bool tried = false;
 };
 static Calib g_calib;  // g_mu NOT required: written once under g_calib_mu
+// Bumped whenever the kernel that calibrate() times changes (2: same-device
+// copies of 64 MiB and more take the streaming kernel); a perf.cal without
+// this version is not trusted.
+constexpr int kCalibVersion = 2;
 static std::mutex g_calib_mu;
 
 static std::string calib_path() {
@@ -136,11 +143,19 @@ static void load_calib_locked() {
   if (!f) return;
   char key[64];
   double val;
+  double same = 0, xgmi = 0;
+  int version = 0;
   while (fscanf(f, "%63s %lf", key, &val) == 2) {
-    if (!strcmp(key, "same_gpu_gbps") && val > 0) g_calib.same_gbps = val;
-    if (!strcmp(key, "xgmi_gbps") && val > 0) g_calib.xgmi_gbps = val;
+    if (!strcmp(key, "version")) version = (int)val;
+    if (!strcmp(key, "same_gpu_gbps") && val > 0) same = val;
+    if (!strcmp(key, "xgmi_gbps") && val > 0) xgmi = val;
   }
   fclose(f);
+  // A file written for another production kernel is stale: ignore it, so
+  // the next calibration overwrites it.
+  if (version != kCalibVersion) return;
+  if (same > 0) g_calib.same_gbps = same;
+  if (xgmi > 0) g_calib.xgmi_gbps = xgmi;
 }
 
 // Timed device copy through the production kernel: dst/src on (possibly
@@ -172,7 +187,7 @@ static double timed_copy_gbps(int dst_dev, int src_dev, size_t nbytes) {
   double best = 0;
   for (int rep = 0; rep < 4; rep++) {
     auto t0 = std::chrono::steady_clock::now();
-    launch_copy(dst, src, nbytes, s);
+    launch_copy(dst, src, nbytes, s, dst_dev == src_dev);
     hipStreamSynchronize(s);
     double dt = std::chrono::duration<double>(
                     std::chrono::steady_clock::now() - t0)
@@ -216,6 +231,7 @@ bool calibrate(bool force, std::string* err) {
     if (!dir.empty()) mkdir(dir.c_str(), 0755);
   }
   if (FILE* f = fopen(path.c_str(), "w")) {
+    fprintf(f, "version %d\n", kCalibVersion);
     fprintf(f, "same_gpu_gbps %.1f\n", g_calib.same_gbps);
     if (g_calib.xgmi_gbps > 0)
       fprintf(f, "xgmi_gbps %.1f\n", g_calib.xgmi_gbps);
@@ -572,7 +588,8 @@ void* begin_pull(const RtsDesc& rts, const BufferRef& dst, uint64_t size,
     // Pull engine selection: gfx950 copy kernel (default) or the SDMA
     // engines via hipMemcpyPeerAsync/hipMemcpyAsync (STARWAY_PULL=sdma).
     // SDMA leaves CUs free and can ride dedicated copy engines; the kernel
-    // reaches 84% of HBM bandwidth and is the measured-fast default.
+    // streams a large same-device message at 6.4 TB/s of HBM traffic
+    // (docs/benchmark.md "Streaming copy") and is the measured-fast default.
     static const bool use_sdma = [] {
       const char* v = getenv("STARWAY_PULL");
       return v && strcmp(v, "sdma") == 0;
@@ -627,7 +644,10 @@ void* begin_pull(const RtsDesc& rts, const BufferRef& dst, uint64_t size,
                            stream);
       }
     } else {
-      e = launch_copy(dst.ptr, src, size, stream);
+      // A source on another GPU (rts.device != run_dev) is an xGMI pull and
+      // keeps the grid-stride kernels: the streaming route was measured
+      // same-device only.
+      e = launch_copy(dst.ptr, src, size, stream, rts.device == run_dev);
     }
   } else {
     if (rts.src_nd.ndim > 0) {
@@ -849,8 +869,12 @@ static CopyTuning resolve_tuning(const CopyTuning& t) {
   if (t.block_cap) r.block_cap = t.block_cap;
   if (t.nt_threshold) r.nt_threshold = t.nt_threshold;
   if (t.nt_unroll) r.nt_unroll = t.nt_unroll;
+  if (t.stream_threshold) r.stream_threshold = t.stream_threshold;
+  if (t.stream_blocks) r.stream_blocks = t.stream_blocks;
   return r;
 }
+
+int copy_stream_unroll() { return sw::copy_stream_unroll(); }
 
 // Take g_mu, switch to `device`, run `launch` on its pull stream and wait.
 template <class Launch>

@@ -39,6 +39,7 @@ int poll_ticket(void*, std::string*) { return -1; }
 void free_ticket(void*) {}
 void synchronize_all() {}
 CopyTuning copy_tuning() { return CopyTuning{8192, (size_t)64 << 20, 4}; }
+int copy_stream_unroll() { return 4; }
 bool copy_device_sync(void*, const void*, size_t, int, const CopyTuning&,
                       std::string* err) {
   *err = "no GPU (sanitizer stub)";

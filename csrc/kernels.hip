@@ -17,11 +17,18 @@
 //    would only add a round trip)
 //  * non-temporal variants for large messages: a message buffer is read and
 //    written exactly once, so polluting L2/LLC with it costs other traffic.
+//  * same-device copies of 64 MiB and more take the tile-contiguous
+//    streaming kernel (copy_stream.hpp) instead: the grid-stride loops
+//    above keep a lane's unrolled accesses one grid stride (32 MiB at 8192
+//    blocks) apart, the streaming kernel sweeps one contiguous window.
+//    Measured at 256 MiB: 84.3 us against 104.6 us, 6.37 against 5.13 TB/s
+//    of HBM traffic (docs/benchmark.md "Streaming copy").
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstdlib>
 
+#include "copy_stream.hpp"
 #include "copy_tuning.hpp"
 #include "layout.hpp"
 
@@ -206,9 +213,19 @@ hipError_t launch_copy_multi(const MultiCopyDesc* descs, int n,
 // Host-side dispatch
 // ---------------------------------------------------------------------------
 
+// The one streaming instantiation production runs, and its defaults: the
+// winner of the alternating sweep recorded in docs/benchmark.md ("Streaming
+// copy"). bin/copy_bench instantiates the whole matrix.
+constexpr int kStreamProdU = 4;
+constexpr int kStreamProdPolicy = kStreamNtNt;
+constexpr bool kStreamProdPrefetch = false;
+constexpr size_t kStreamDefaultThreshold = (size_t)64 << 20;
+constexpr size_t kStreamDefaultBlocks = 8192;
+
 const CopyTuning& default_copy_tuning() {
   // Read once per process; STARWAY_COPY_BLOCKS / STARWAY_NT_THRESHOLD /
-  // STARWAY_COPY_UNROLL exist for on-box sweeps (scripts/copy_tune.sh).
+  // STARWAY_COPY_UNROLL / STARWAY_STREAM_THRESHOLD / STARWAY_STREAM_BLOCKS
+  // exist for on-box sweeps (scripts/copy_tune.sh).
   static const CopyTuning t = [] {
     CopyTuning d;
     const char* v = getenv("STARWAY_COPY_BLOCKS");
@@ -219,6 +236,12 @@ const CopyTuning& default_copy_tuning() {
         v && *v ? (size_t)strtoull(v, nullptr, 10) : (size_t)64 << 20;
     v = getenv("STARWAY_COPY_UNROLL");
     d.nt_unroll = v && *v ? atoi(v) : 4;
+    v = getenv("STARWAY_STREAM_THRESHOLD");
+    d.stream_threshold = v && *v ? (size_t)strtoull(v, nullptr, 10)
+                                 : kStreamDefaultThreshold;
+    v = getenv("STARWAY_STREAM_BLOCKS");
+    d.stream_blocks = v && *v ? (size_t)strtoull(v, nullptr, 10)
+                              : kStreamDefaultBlocks;
     return d;
   }();
   return t;
@@ -231,6 +254,8 @@ static inline int copy_grid(size_t work_items, size_t cap) {
   if (blocks > cap) blocks = cap;
   return (int)blocks;
 }
+
+int copy_stream_unroll() { return kStreamProdU; }
 
 hipError_t launch_copy_tuned(void* dst, const void* src, size_t bytes,
                              hipStream_t stream, const CopyTuning& t) {
@@ -251,7 +276,14 @@ hipError_t launch_copy_tuned(void* dst, const void* src, size_t bytes,
     size_t n16 = bytes / 16;
     size_t tail = bytes & 15;
     if (n16) {
-      if (bytes >= t.nt_threshold) {
+      if (n16 * 16 >= t.stream_threshold) {
+        hipError_t e =
+            launch_copy_stream<kStreamProdU, kStreamProdPolicy,
+                               kStreamProdPrefetch>(
+                (void*)d, (const void*)s, n16,
+                t.stream_blocks ? t.stream_blocks : 1, stream);
+        if (e != hipSuccess) return e;
+      } else if (bytes >= t.nt_threshold) {
         if (t.nt_unroll >= 8) {
           hipLaunchKernelGGL(k_copy_b128_nt_u8,
                              dim3(copy_grid(n16 / 8 + 1, cap)), dim3(256), 0,
@@ -286,8 +318,15 @@ hipError_t launch_copy_tuned(void* dst, const void* src, size_t bytes,
 }
 
 hipError_t launch_copy(void* dst, const void* src, size_t bytes,
-                       hipStream_t stream) {
-  return launch_copy_tuned(dst, src, bytes, stream, default_copy_tuning());
+                       hipStream_t stream, bool same_device) {
+  if (same_device)
+    return launch_copy_tuned(dst, src, bytes, stream, default_copy_tuning());
+  // The streaming route was measured only for same-device copies; nothing
+  // here can measure a pull over xGMI, and an unmeasured path does not
+  // change: a cross-device pull keeps the grid-stride kernels.
+  CopyTuning t = default_copy_tuning();
+  t.stream_threshold = kStreamNever;
+  return launch_copy_tuned(dst, src, bytes, stream, t);
 }
 
 hipError_t launch_copy_strided_tuned(void* dst, uint64_t dst_stride,

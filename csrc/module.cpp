@@ -6,6 +6,7 @@
 // (__cuda_array_interface__, e.g. torch HIP tensors) — the reference was
 // CPU-only (nb::device::cpu, main.hpp:155) and left GPU "planned".
 #include "core.hpp"
+#include "copy_stream.hpp"
 
 #include <pybind11/functional.h>
 #include <pybind11/stl.h>
@@ -417,20 +418,24 @@ PYBIND11_MODULE(_core, m) {
   // variant and a capped (multi-iteration) grid at small sizes.
   m.def("_copy_device_sync",
         [](uintptr_t dst, uintptr_t src, size_t nbytes, int device,
-           size_t block_cap, size_t nt_threshold, int nt_unroll) {
+           size_t block_cap, size_t nt_threshold, int nt_unroll,
+           size_t stream_threshold, size_t stream_blocks) {
           std::string err;
           bool ok;
           {
             py::gil_scoped_release rel;
             ok = gpu::copy_device_sync(
                 (void*)dst, (const void*)src, nbytes, device,
-                CopyTuning{block_cap, nt_threshold, nt_unroll}, &err);
+                CopyTuning{block_cap, nt_threshold, nt_unroll,
+                           stream_threshold, stream_blocks},
+                &err);
           }
           if (!ok) throw std::runtime_error("copy_device_sync: " + err);
         },
         py::arg("dst"), py::arg("src"), py::arg("nbytes"), py::arg("device"),
         py::arg("block_cap") = 0, py::arg("nt_threshold") = 0,
-        py::arg("nt_unroll") = 0);
+        py::arg("nt_unroll") = 0, py::arg("stream_threshold") = 0,
+        py::arg("stream_blocks") = 0);
   m.def("_copy_strided_sync",
         [](uintptr_t dst, uint64_t dst_stride, uintptr_t src,
            uint64_t src_stride, uint64_t rows, uint64_t row_bytes, int device,
@@ -544,6 +549,46 @@ PYBIND11_MODULE(_core, m) {
     d["nt_unroll"] = t.nt_unroll;
     return d;
   });
+  // Streaming-kernel defaults (copy_stream.hpp), kept out of _copy_tuning()
+  // so that dict stays exactly its three keys. "unroll" is the production
+  // kernel's U: a tile is 256 * unroll elements of 16 B. Host-only.
+  m.def("_copy_stream_tuning", [] {
+    CopyTuning t = gpu::copy_tuning();
+    py::dict d;
+    d["stream_threshold"] = t.stream_threshold;
+    d["stream_blocks"] = t.stream_blocks;
+    d["unroll"] = gpu::copy_stream_unroll();
+    return d;
+  });
+  // Tile plan of the production streaming kernel for n16 bulk elements
+  // under a grid cap (0 = the process default). With `block`, also that
+  // workgroup's tiles: first_tile, first_tile + grid, ..., last_tile
+  // (n_tiles of them). Host-only.
+  m.def("_copy_stream_plan",
+        [](uint64_t n16, uint64_t stream_blocks, py::object block) {
+          if (stream_blocks == 0)
+            stream_blocks = gpu::copy_tuning().stream_blocks;
+          if (stream_blocks == 0)
+            throw py::value_error("copy_stream_plan: stream_blocks is 0");
+          const StreamPlan p = stream_plan(
+              n16, (uint32_t)gpu::copy_stream_unroll(), stream_blocks);
+          py::dict d;
+          d["tile"] = p.tile;
+          d["full_tiles"] = p.full_tiles;
+          d["ragged"] = p.ragged;
+          d["tiles"] = p.tiles;
+          d["grid"] = p.grid;
+          if (!block.is_none()) {
+            const StreamBlockTiles b =
+                stream_block_tiles(p, block.cast<uint64_t>());
+            d["first_tile"] = b.first;
+            d["last_tile"] = b.last;
+            d["n_tiles"] = b.count;
+          }
+          return d;
+        },
+        py::arg("n16"), py::arg("stream_blocks") = 0,
+        py::arg("block") = py::none());
   // Test hooks for the small-message kernels (smallmsg.hip). They go
   // through the host functions the engine uses (inbox_create, same-process
   // inbox_push, inbox_unpack, arm_recv's two halves, arm_poll / arm_cancel
