@@ -19,6 +19,10 @@ struct CopyTuning {
   size_t stream_threshold = 0;  // bulk bytes at/above which it runs
                                 // (STARWAY_STREAM_THRESHOLD)
   size_t stream_blocks = 0;     // its grid cap (STARWAY_STREAM_BLOCKS)
+  // Accumulate kernels (reducing receive): bulk bytes at/above which the
+  // SOURCE loads are non-temporal (STARWAY_ACCUM_NT_THRESHOLD). Its own
+  // knob: the read-modify-write kernel crosses over far above the copies.
+  size_t accum_nt_threshold = 0;
 };
 
 // stream_threshold value that no message reaches: the streaming kernel off.
@@ -29,7 +33,8 @@ constexpr size_t kStreamNever = ~(size_t)0;
 enum class CopyNdPath : int { Auto = 0, Generic = 1, Tiled = 2 };
 
 // Environment-derived default (8192 blocks, 64 MiB, x4; streaming kernel
-// from 64 MiB, 8192 blocks), read once per process. Host-only: never
+// from 64 MiB, 8192 blocks; accumulate NT source loads from 192 MiB), read
+// once per process. Host-only: never
 // touches the GPU.
 const CopyTuning& default_copy_tuning();
 

@@ -30,6 +30,7 @@
 #include <pybind11/pybind11.h>
 
 #include "copy_tuning.hpp"
+#include "elem_type.hpp"
 #include "layout.hpp"
 
 namespace py = pybind11;
@@ -160,6 +161,8 @@ const uint8_t* process_uuid();  // 16 bytes, stable for this process
 // Buffers
 // ---------------------------------------------------------------------------
 
+enum class ReduceOp : uint8_t { None = 0, Sum };
+
 // A caller-provided message buffer. device < 0 => host memory.
 // rows > 0 => 2D-strided device buffer (non-contiguous tensor): the
 // message is rows x row_bytes dense bytes, row r starting at
@@ -174,11 +177,26 @@ struct BufferRef {
   uint64_t row_bytes = 0;
   uint64_t stride = 0;
   Layout nd{};
+  // Reducing receive (recv side only): delivery adds the message, read as
+  // elements of `elem`, into the buffer instead of overwriting it. Set only
+  // on a dense device buffer whose ptr is aligned to the element size.
+  ReduceOp reduce = ReduceOp::None;
+  ElemType elem = ElemType::None;
   // One dense run of `size` bytes at ptr. Anything else is packed or
   // unpacked by a copy kernel: it stays off the inbox push plane and the
   // doorbell, takes the bounce path for eager/inbox/CMA deliveries and
   // needs the exact message size.
   bool dense() const { return rows == 0 && nd.ndim == 0; }
+  bool reducing() const { return reduce != ReduceOp::None; }
+  // Dense, and delivery overwrites: only such a device buffer may be
+  // written by a copy that does not go through begin_pull or begin_h2d
+  // (k_copy_multi, the inbox unpack kernel, the doorbell). A reducing
+  // buffer is delivered through those two alone: they accumulate.
+  bool plain() const { return dense() && !reducing(); }
+  // A reducing receive takes whole elements only.
+  bool whole_elems(uint64_t len) const {
+    return !reducing() || len % elem_size(elem) == 0;
+  }
   // This buffer as a Layout, for a copy whose other side is N-D.
   Layout layout() const {
     if (nd.ndim > 0) return nd;
@@ -453,6 +471,8 @@ class Engine {
     std::atomic<uint64_t> eager_rx{0}, gpu_rx{0}, cma_rx{0};
     std::atomic<uint64_t> inbox_rx{0}, inbox_tx{0};  // small-message plane
     std::atomic<uint64_t> doorbell_rx{0};            // of inbox_rx, pre-armed
+    // Delivered reducing receives; each also counts on its plane.
+    std::atomic<uint64_t> reduce_rx{0};
     std::atomic<uint64_t> unexpected_rx{0};
     std::atomic<uint64_t> unexp_staged_bytes{0};  // flow-control watermark
     std::atomic<uint64_t> deferred_sends{0};      // window-queued sends
@@ -520,9 +540,11 @@ class Engine {
                       const std::string& err);
   void reject_rndv(Connection* c, uint64_t sender_op, Op* recv,
                    const std::string& err);
-  // Host bounce -> device recv buffer; the recv completes in poll_gpu.
-  // Fails the op and returns false when the upload cannot start.
-  bool upload_to_recv(Op* r, uint64_t tag, uint64_t len, RawBuf&& bounce);
+  // Host bounce -> device recv buffer; the recv completes in poll_gpu and
+  // counts on `plane`. Fails the op and returns false when the upload
+  // cannot start.
+  bool upload_to_recv(Op* r, uint64_t tag, uint64_t len, RawBuf&& bounce,
+                      RxPlane plane = RxPlane::Gpu);
   UnexpectedMsg* park_unexpected(Connection* c, uint64_t tag, uint64_t size,
                                  uint64_t sender_op);
   bool unpost_recv(Op* r);  // false => r was not posted
@@ -585,6 +607,8 @@ class Engine {
     uint64_t sender_op_id;
     uint64_t tag;
     uint64_t size;
+    // What the delivery counts as when the ticket lands.
+    RxPlane plane = RxPlane::Gpu;
   };
   std::vector<SmallPull> pending_small_pulls_;
   void flush_small_pulls();
@@ -721,7 +745,9 @@ int current_device();  // calling thread's device, -1 without GPU
 // Fill an RtsDesc for a device buffer (ipc handle or raw ptr).
 bool make_rts(const BufferRef& buf, RtsDesc* out, std::string* err);
 // Begin an async pull of `size` bytes described by `rts` into dst (host or
-// device). Returns an opaque ticket (hipEvent) or null on error.
+// device). Returns an opaque ticket (hipEvent) or null on error. A reducing
+// dst is accumulated into (k_accum_*), on lane 0 of its device whatever the
+// source; STARWAY_PULL=sdma does not apply to it.
 void* begin_pull(const RtsDesc& rts, const BufferRef& dst, uint64_t size,
                  std::string* err);
 // Batched small-message pull: one launch + one event for up to 8 messages
@@ -736,7 +762,8 @@ struct PullReq {
 void* begin_pull_multi(const PullReq* reqs, int n, std::string* err);
 // Begin an async host->device upload into a device buffer. The host memory
 // must stay valid until the ticket completes; hand its ownership to the
-// ticket with attach_bounce.
+// ticket with attach_bounce. A reducing dst: host -> device staging, then
+// accumulate from staging, on the same stream.
 void* begin_h2d(const BufferRef& dst, const void* src, uint64_t size,
                 std::string* err);
 // Device -> host staging download (cross-host GPU sends).
@@ -824,6 +851,11 @@ struct CopyDesc {
 };
 bool copy_multi_sync(const CopyDesc* descs, int n, int device,
                      std::string* err);
+// The accumulate kernels (launch_accum_tuned): dst[i] += src[i] over
+// nbytes / elem_size(dtype) elements. Refuses pointers or a length that
+// are not multiples of the element size.
+bool accum_sync(void* dst, const void* src, size_t nbytes, ElemType dtype,
+                int device, const CopyTuning& tuning, std::string* err);
 // Test hooks for the inbox kernels (smallmsg.hip). They drive the kernels
 // through the host functions above (same-process push, lane 0) and wait
 // under a host deadline; none of them launches a kernel of its own.

@@ -797,6 +797,8 @@ void Engine::deliver_recv(Op* r, uint64_t tag, uint64_t len, RxPlane plane) {
       stats_.inbox_rx.fetch_add(1, std::memory_order_relaxed);
       break;
   }
+  if (r->buf.reducing())
+    stats_.reduce_rx.fetch_add(1, std::memory_order_relaxed);
   Completion comp;
   comp.kind = Completion::Kind::RecvDone;
   comp.op = r;

@@ -40,6 +40,8 @@ PeerInfo self_peer_info(const std::string& name);
 bool inbox_enabled();  // STARWAY_INBOX, cached at first use; engine_wire.cpp
 uint64_t unexp_cap();  // STARWAY_UNEXP_CAP, cached; engine_match.cpp
 std::string truncated_msg(uint64_t len, uint64_t cap);  // engine_match.cpp
+// A message a reducing recv cannot take: not whole elements.
+std::string reduce_len_msg(uint64_t len, const BufferRef& buf);
 bool flush_forgets_any(Op* f, const std::vector<uint64_t>& ids);
 
 // Bounded wait: polls step() while it reports "still pending", for at most

@@ -20,6 +20,12 @@ std::string truncated_msg(uint64_t len, uint64_t cap) {
          std::to_string(cap) + ")";
 }
 
+std::string reduce_len_msg(uint64_t len, const BufferRef& buf) {
+  return "reduce: message length " + std::to_string(len) +
+         " B is not a multiple of the item size (" +
+         std::to_string(elem_size(buf.elem)) + " B)";
+}
+
 void Engine::unstage_unexp(UnexpectedMsg* um) {
   if (!um->staged) return;
   if (um->conn) um->conn->unexp_staged_bytes -= um->staged;
@@ -163,6 +169,10 @@ void Engine::complete_recv_from_unexpected(Op* op, UnexpectedMsg* um) {
   if (um->size > op->buf.size ||
       (op->buf.nd.ndim > 0 && um->size != op->buf.size)) {
     fail_op(op, "receive failed: " + truncated_msg(um->size, op->buf.size));
+    return;
+  }
+  if (!op->buf.whole_elems(um->size)) {
+    fail_op(op, "receive failed: " + reduce_len_msg(um->size, op->buf));
     return;
   }
   if (op->buf.device >= 0) {

@@ -35,12 +35,17 @@ void Engine::start_gpu_pull(Op* recv_op, const RtsDesc& rts, uint64_t tag,
     reject_rndv(c, sender_op, recv_op, truncated_msg(size, recv_op->buf.size));
     return;
   }
+  if (!recv_op->buf.whole_elems(size)) {
+    reject_rndv(c, sender_op, recv_op, reduce_len_msg(size, recv_op->buf));
+    return;
+  }
   // Small contiguous device->device messages are batched: collected here,
   // launched as one multi-copy kernel + one event at the end of the loop
-  // iteration (the per-launch cost dominates small-message rate).
+  // iteration (the per-launch cost dominates small-message rate). Never a
+  // reducing recv: k_copy_multi overwrites.
   static const uint64_t kMultiMax = env_u64("STARWAY_MULTI_COPY_MAX", 65536);
   if (size > 0 && size <= kMultiMax && recv_op->buf.device >= 0 &&
-      recv_op->buf.dense() && rts.src_rows == 0 && rts.src_nd.ndim == 0) {
+      recv_op->buf.plain() && rts.src_rows == 0 && rts.src_nd.ndim == 0) {
     pending_small_pulls_.push_back(
         SmallPull{rts, recv_op, c, sender_op, tag, size});
     return;
@@ -62,7 +67,7 @@ void Engine::track_gpu_ticket(void* ticket, std::vector<SmallPull> items) {
 }
 
 bool Engine::upload_to_recv(Op* r, uint64_t tag, uint64_t len,
-                            RawBuf&& bounce) {
+                            RawBuf&& bounce, RxPlane plane) {
   std::string err;
   void* ticket = gpu::begin_h2d(r->buf, bounce.data(), len, &err);
   if (!ticket) {
@@ -70,10 +75,12 @@ bool Engine::upload_to_recv(Op* r, uint64_t tag, uint64_t len,
     return false;
   }
   // The ticket owns the bounce until the copy lands. No sender op: the
-  // upload completes through poll_gpu (counted as gpu_rx) and acks nobody.
+  // upload completes through poll_gpu (counted on `plane`, gpu_rx unless
+  // the caller says otherwise) and acks nobody.
   gpu::attach_bounce(ticket, std::move(bounce));
   bounce.clear();
-  track_gpu_ticket(ticket, {SmallPull{RtsDesc{}, r, nullptr, 0, tag, len}});
+  track_gpu_ticket(ticket,
+                   {SmallPull{RtsDesc{}, r, nullptr, 0, tag, len, plane}});
   return true;
 }
 
@@ -132,7 +139,8 @@ void Engine::inbox_release_seq(Connection* c, uint64_t seq) {
 }
 
 // Route one announced inbox message to a matched recv: batched local
-// unpack kernel (device dst) or pinned bounce (host / strided dst).
+// unpack kernel (device dst) or pinned bounce (host / strided / reducing
+// dst; the unpack kernel overwrites).
 void Engine::dispatch_smsg_to_recv(Connection* c, Op* r, uint64_t tag,
                                    uint64_t size, uint64_t seq) {
   if (size > r->buf.size || (!r->buf.dense() && size != r->buf.size)) {
@@ -140,8 +148,13 @@ void Engine::dispatch_smsg_to_recv(Connection* c, Op* r, uint64_t tag,
     inbox_release_seq(c, seq);  // discard without reading the slot
     return;
   }
+  if (!r->buf.whole_elems(size)) {
+    fail_op(r, "receive failed: " + reduce_len_msg(size, r->buf));
+    inbox_release_seq(c, seq);
+    return;
+  }
   uint8_t* dst = nullptr;
-  if (r->buf.device >= 0 && r->buf.dense() &&
+  if (r->buf.device >= 0 && r->buf.plain() &&
       r->buf.device == c->inbox_l.device)
     dst = r->buf.ptr;
   pending_unpacks_.push_back(PendingUnpack{c, seq, size, tag, r, dst});
@@ -387,7 +400,13 @@ void Engine::progress_unpacks(bool& did_work) {
             fail_op(m.recv_op, "receive failed: bounce allocation failed");
           } else {
             memcpy(heap.data(), bounce, m.size);
-            upload_to_recv(m.recv_op, m.tag, m.size, std::move(heap));
+            // Every inbox message for a reducing recv comes this way, and
+            // counts as what it is, once, when it is delivered: inbox_rx.
+            // (A plain strided / other-device recv on this path has always
+            // counted as gpu_rx, and still does.)
+            upload_to_recv(m.recv_op, m.tag, m.size, std::move(heap),
+                           m.recv_op->buf.reducing() ? RxPlane::Inbox
+                                                     : RxPlane::Gpu);
           }
           inbox_release_seq(m.conn, m.seq);
           continue;
@@ -421,7 +440,8 @@ void Engine::try_arm() {
   // arm launch + inline wait per message.
   if (posted_recvs_.size() != 1) return;
   Op* r = posted_recvs_.front();
-  if (r->buf.device < 0 || !r->buf.dense() || r->buf.size == 0) return;
+  // A reducing recv is never armed: the wait kernel overwrites.
+  if (r->buf.device < 0 || !r->buf.plain() || r->buf.size == 0) return;
   // Only safe with exactly one live connection (its inbox FIFO is then the
   // only source of inbox messages that could race the doorbell).
   Connection* target = nullptr;
@@ -481,6 +501,10 @@ void Engine::start_cma_pull(Op* recv_op, const CmaDesc& cma, uint64_t tag,
   if (size > recv_op->buf.size ||
       (!recv_op->buf.dense() && size != recv_op->buf.size)) {
     reject_rndv(c, sender_op, recv_op, truncated_msg(size, recv_op->buf.size));
+    return;
+  }
+  if (!recv_op->buf.whole_elems(size)) {
+    reject_rndv(c, sender_op, recv_op, reduce_len_msg(size, recv_op->buf));
     return;
   }
   auto pull = std::make_unique<CmaPull>();
@@ -626,7 +650,7 @@ void Engine::poll_gpu(bool& did_work) {
         if (it.sender_op_id && it.conn && !it.conn->dead)
           enqueue_frame(it.conn, FT_RECV_DONE, 0, it.sender_op_id, 0, nullptr,
                         0, true);
-        deliver_recv(it.recv_op, it.tag, it.size, RxPlane::Gpu);
+        deliver_recv(it.recv_op, it.tag, it.size, it.plane);
       } else {
         reject_rndv(it.conn, it.sender_op_id, it.recv_op, err);
       }

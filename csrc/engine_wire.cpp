@@ -882,8 +882,10 @@ void Engine::begin_eager(Connection* c) {
   if (Op* r = take_matching_recv(tag)) {
     {
       if (msg_len > r->buf.size ||
-          (!r->buf.dense() && msg_len != r->buf.size)) {
-        // Truncation / strided-geometry mismatch: consume + fail
+          (!r->buf.dense() && msg_len != r->buf.size) ||
+          !r->buf.whole_elems(msg_len)) {
+        // Truncation / strided-geometry mismatch / a reducing recv offered
+        // part of an element: consume + fail
         // (UCX MESSAGE_TRUNCATED analog; a strided window needs the exact
         // message size or partial rows would smear).
         c->rx_truncated = true;
@@ -948,7 +950,13 @@ void Engine::finish_eager_into_recv(Connection* c) {
     c->rx_recv_op = nullptr;
     if (c->rx_truncated) {
       c->rx_truncated = false;
-      fail_op(r, "receive failed: " + truncated_msg(r->recv_len, r->buf.size));
+      // Same order as every other plane: too long first.
+      const bool fits =
+          r->recv_len <= r->buf.size &&
+          (r->buf.dense() || r->recv_len == r->buf.size);
+      fail_op(r, "receive failed: " +
+                     (fits ? reduce_len_msg(r->recv_len, r->buf)
+                           : truncated_msg(r->recv_len, r->buf.size)));
       return;
     }
     if (r->buf.device >= 0) {

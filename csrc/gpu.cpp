@@ -50,6 +50,13 @@ hipError_t launch_copy_nd_tuned(void* dst, const Layout& dst_layout,
                                 uint64_t bytes, hipStream_t stream,
                                 const CopyTuning& t, CopyNdPath path);
 int copy_nd_tile_extent(int elem_bytes);
+// dst[i] += src[i]; both pointers aligned to the element size, bytes a
+// multiple of it, no overlap.
+hipError_t launch_accum(void* dst, const void* src, size_t bytes,
+                        ElemType dtype, hipStream_t stream);
+hipError_t launch_accum_tuned(void* dst, const void* src, size_t bytes,
+                              ElemType dtype, hipStream_t stream,
+                              const CopyTuning& t);
 bool copy_nd_tile_eligible(const Layout& src_layout, const Layout& dst_layout,
                            const void* src, const void* dst);
 
@@ -547,8 +554,11 @@ static void log_route_once(int run_dev, const RtsDesc& rts, bool same_proc,
     return !(v && !strcmp(v, "0"));
   }();
   if (!enabled) return;
-  static std::set<std::tuple<int, int, int>> seen;  // g_mu held by callers
-  if (!seen.insert({run_dev, rts.device, (int)same_proc}).second) return;
+  // g_mu held by callers. The engine is part of the key: a copy route
+  // and an accumulate route over one device pair each get their line.
+  static std::set<std::tuple<int, int, int, std::string>> seen;
+  if (!seen.insert({run_dev, rts.device, (int)same_proc, engine}).second)
+    return;
   fprintf(stderr,
           "[starway] route: pull dev%d <- peer dev%d (%s, %s) lane=%d "
           "engine=%s\n",
@@ -578,10 +588,64 @@ void* begin_pull(const RtsDesc& rts, const BufferRef& dst, uint64_t size,
   // across xGMI links. Same-device peers (shared-GPU emulation) share a
   // lane, which also keeps the per-device HSA queue count low there.
   int lane = rts.device & (stream_lanes() - 1);
+  // Every accumulate into one device rides ONE stream, lane 0 (begin_h2d's
+  // too), not the per-source-device lane: two read-modify-write kernels on
+  // one buffer must never overlap, and any number of reducing receives
+  // into the same buffer may be in flight, from any mix of peers.
+  if (dst.reducing()) lane = 0;
   hipStream_t stream = pull_stream(run_dev, lane);
   hipError_t e;
   void* staging = nullptr;
-  if (dst.device >= 0) {
+  if (dst.device >= 0 && dst.reducing()) {
+    bool same_proc = memcmp(rts.src_uuid, process_uuid(), 16) == 0;
+    if (same_proc) ensure_peer_access(dst.device, rts.device);
+    log_route_once(run_dev, rts, same_proc, lane, "gfx950_accum");
+    const size_t es = elem_size(dst.elem);
+    if (!dst.dense() || es == 0 || (uintptr_t)dst.ptr % es || size % es ||
+        size > dst.size) {
+      hipSetDevice(prev);
+      *err = "reduce: destination or message length does not fit the "
+             "element type";
+      return nullptr;
+    }
+    const bool packed = rts.src_rows == 0 && rts.src_nd.ndim == 0;
+    if (packed && (uintptr_t)src % es == 0) {
+      // Fast route: the accumulate kernel reads the source where it lies
+      // (peer memory over xGMI, hipIpc-mapped, or local).
+      e = launch_accum(dst.ptr, src, size, dst.elem, stream);
+    } else {
+      // Slow route (rows, N-D or element-misaligned source): pack into
+      // contiguous device staging with the copy kernels, then accumulate
+      // from staging; same stream, so in order.
+      // Staging holds `size` bytes: the peer's geometry must describe
+      // exactly that many.
+      Layout sl{};
+      if (rts.src_nd.ndim > 0 && !rts_layout(rts, size, &sl, err)) {
+        hipSetDevice(prev);
+        return nullptr;
+      }
+      if (rts.src_rows > 0 && rts.src_rows * rts.src_row_bytes != size) {
+        hipSetDevice(prev);
+        *err = "malformed strided source layout in RTS";
+        return nullptr;
+      }
+      e = alloc_staging(size, &staging);
+      if (e == hipSuccess) {
+        if (rts.src_nd.ndim > 0)
+          e = launch_copy_nd(staging, contiguous_layout(size), src, sl, size,
+                             stream);
+        else if (rts.src_rows > 0)
+          e = launch_copy_strided(staging, rts.src_row_bytes, src,
+                                  rts.src_stride, rts.src_rows,
+                                  rts.src_row_bytes, stream);
+        else
+          e = launch_copy(staging, src, size, stream,
+                          rts.device == run_dev);
+      }
+      if (e == hipSuccess)
+        e = launch_accum(dst.ptr, staging, size, dst.elem, stream);
+    }
+  } else if (dst.device >= 0) {
     bool same_proc = memcmp(rts.src_uuid, process_uuid(), 16) == 0;
     if (same_proc) ensure_peer_access(dst.device, rts.device);
     log_route_once(run_dev, rts, same_proc, lane, "gfx950_copy");
@@ -749,7 +813,26 @@ void* begin_h2d(const BufferRef& dst, const void* src, uint64_t size,
   hipStream_t stream = pull_stream(dst.device);
   hipError_t e;
   void* staging = nullptr;
-  if (dst.nd.ndim > 0) {
+  if (dst.reducing()) {
+    // pull_stream(device) is lane 0: the one stream all accumulates into
+    // this device share (see begin_pull).
+    const size_t es = elem_size(dst.elem);
+    if (!dst.dense() || es == 0 || (uintptr_t)dst.ptr % es || size % es ||
+        size > dst.size) {
+      hipSetDevice(prev);
+      *err = "reduce: destination or message length does not fit the "
+             "element type";
+      return nullptr;
+    }
+    e = hipSuccess;
+    if (size > 0) {
+      e = alloc_staging(size, &staging);
+      if (e == hipSuccess)
+        e = hipMemcpyAsync(staging, src, size, hipMemcpyHostToDevice, stream);
+      if (e == hipSuccess)
+        e = launch_accum(dst.ptr, staging, size, dst.elem, stream);
+    }
+  } else if (dst.nd.ndim > 0) {
     if (size != dst.size) {
       hipSetDevice(prev);
       *err = "strided recv buffer geometry mismatch (buffer " +
@@ -871,6 +954,7 @@ static CopyTuning resolve_tuning(const CopyTuning& t) {
   if (t.nt_unroll) r.nt_unroll = t.nt_unroll;
   if (t.stream_threshold) r.stream_threshold = t.stream_threshold;
   if (t.stream_blocks) r.stream_blocks = t.stream_blocks;
+  if (t.accum_nt_threshold) r.accum_nt_threshold = t.accum_nt_threshold;
   return r;
 }
 
@@ -935,6 +1019,19 @@ bool copy_nd_sync(void* dst, const Layout& dst_layout, const void* src,
 
 int copy_nd_tile_extent(int elem_bytes) {
   return sw::copy_nd_tile_extent(elem_bytes);
+}
+
+bool accum_sync(void* dst, const void* src, size_t nbytes, ElemType dtype,
+                int device, const CopyTuning& tuning, std::string* err) {
+  const size_t es = elem_size(dtype);
+  if (es == 0 || nbytes % es || ((uintptr_t)dst | (uintptr_t)src) % es) {
+    *err = "pointers and length must be multiples of the element size";
+    return false;
+  }
+  CopyTuning t = resolve_tuning(tuning);
+  return run_sync(device, err, [&](hipStream_t stream) {
+    return launch_accum_tuned(dst, src, nbytes, dtype, stream, t);
+  });
 }
 
 // Callers validate 1 <= n <= 8 and bytes < 2^32 (launch_copy_multi does not).

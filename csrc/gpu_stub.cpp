@@ -62,6 +62,11 @@ bool copy_multi_sync(const CopyDesc*, int, int, std::string* err) {
   *err = "no GPU (sanitizer stub)";
   return false;
 }
+bool accum_sync(void*, const void*, size_t, ElemType, int, const CopyTuning&,
+                std::string* err) {
+  *err = "no GPU (sanitizer stub)";
+  return false;
+}
 double same_gpu_copy_gbps() { return 3100.0; }
 double xgmi_link_gbps() { return 140.0; }
 bool calibrate(bool, std::string* err) {

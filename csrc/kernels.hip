@@ -30,6 +30,7 @@
 
 #include "copy_stream.hpp"
 #include "copy_tuning.hpp"
+#include "elem_type.hpp"
 #include "layout.hpp"
 
 namespace sw {
@@ -221,6 +222,15 @@ constexpr int kStreamProdPolicy = kStreamNtNt;
 constexpr bool kStreamProdPrefetch = false;
 constexpr size_t kStreamDefaultThreshold = (size_t)64 << 20;
 constexpr size_t kStreamDefaultBlocks = 8192;
+// Accumulate kernels: non-temporal source loads from this size. Swept on
+// MI355X, same device, both variants forced, fp32 / bf16, median of 9
+// rounds x 10 calls (docs/benchmark.md "Reducing receive"): the plain
+// loads are faster up to 128 MiB (by 4-6 % at 64 MiB), the two are level
+// at 160 MiB (within 2 % either way), and from 192 MiB the non-temporal
+// loads win with the ranges apart (6-7 % at 192 MiB, 13-14 % at 224 MiB,
+// 20-24 % at 256 MiB). 192 MiB is the smallest measured size where they
+// win for both types.
+constexpr size_t kAccumNtDefaultThreshold = (size_t)192 << 20;
 
 const CopyTuning& default_copy_tuning() {
   // Read once per process; STARWAY_COPY_BLOCKS / STARWAY_NT_THRESHOLD /
@@ -242,6 +252,9 @@ const CopyTuning& default_copy_tuning() {
     v = getenv("STARWAY_STREAM_BLOCKS");
     d.stream_blocks = v && *v ? (size_t)strtoull(v, nullptr, 10)
                               : kStreamDefaultBlocks;
+    v = getenv("STARWAY_ACCUM_NT_THRESHOLD");
+    d.accum_nt_threshold = v && *v ? (size_t)strtoull(v, nullptr, 10)
+                                   : kAccumNtDefaultThreshold;
     return d;
   }();
   return t;
@@ -670,6 +683,202 @@ hipError_t launch_copy_nd(void* dst, const Layout& dl, const void* src,
                           hipStream_t stream) {
   return launch_copy_nd_tuned(dst, dl, src, sl, bytes, stream,
                               default_copy_tuning(), CopyNdPath::Auto);
+}
+
+// ---------------------------------------------------------------------------
+// Accumulate family (reducing receive): dst[i] = dst[i] + src[i]. Same
+// shape as the copy family (256-thread workgroups, 16 B per lane, grid
+// stride, x4 unroll, no LDS: nothing is reused), but the destination is
+// read as well as written, so a message costs three memory streams.
+//
+// The 2-byte types widen each element to fp32, add there and round once to
+// nearest even: exactly (dst.float() + src.float()).to(dtype). Subnormals
+// are kept (the default kernel mode; never build this file with
+// flush-to-zero).
+// ---------------------------------------------------------------------------
+
+using f32x2 = __attribute__((ext_vector_type(2))) float;
+using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
+using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
+
+// One tag per element type: W is the element's storage word, add() works
+// on one element, add32() on the 32-bit word of a 16 B vector.
+struct AccF32 {
+  using W = uint32_t;
+  static __device__ __forceinline__ W add(W d, W s) {
+    return __float_as_uint(__uint_as_float(d) + __uint_as_float(s));
+  }
+  static __device__ __forceinline__ uint32_t add32(uint32_t d, uint32_t s) {
+    return add(d, s);
+  }
+};
+
+struct AccI32 {
+  using W = uint32_t;
+  static __device__ __forceinline__ W add(W d, W s) { return d + s; }
+  static __device__ __forceinline__ uint32_t add32(uint32_t d, uint32_t s) {
+    return d + s;
+  }
+};
+
+struct AccF16 {
+  using W = uint16_t;
+  static __device__ __forceinline__ W add(W d, W s) {
+    const float r = (float)__builtin_bit_cast(_Float16, d) +
+                    (float)__builtin_bit_cast(_Float16, s);
+    return __builtin_bit_cast(W, (_Float16)r);
+  }
+  static __device__ __forceinline__ uint32_t add32(uint32_t d, uint32_t s) {
+    const f32x2 r =
+        __builtin_convertvector(__builtin_bit_cast(f16x2, d), f32x2) +
+        __builtin_convertvector(__builtin_bit_cast(f16x2, s), f32x2);
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(r, f16x2));
+  }
+};
+
+struct AccBF16 {
+  using W = uint16_t;
+  // A bf16 is the top half of an fp32: widening is a shift. The narrowing
+  // conversion is the compiler's (v_cvt_pk_bf16_f32 on gfx950).
+  static __device__ __forceinline__ W add(W d, W s) {
+    const float r = __uint_as_float((uint32_t)d << 16) +
+                    __uint_as_float((uint32_t)s << 16);
+    return __builtin_bit_cast(W, (__bf16)r);
+  }
+  static __device__ __forceinline__ uint32_t add32(uint32_t d, uint32_t s) {
+    f32x2 r;
+    r.x = __uint_as_float(d << 16) + __uint_as_float(s << 16);
+    r.y = __uint_as_float(d & 0xffff0000u) + __uint_as_float(s & 0xffff0000u);
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(r, bf16x2));
+  }
+};
+
+template <class A>
+__device__ __forceinline__ u32x4 accum16(u32x4 d, u32x4 s) {
+  u32x4 r;
+  r.x = A::add32(d.x, s.x);
+  r.y = A::add32(d.y, s.y);
+  r.z = A::add32(d.z, s.z);
+  r.w = A::add32(d.w, s.w);
+  return r;
+}
+
+// Source load of the bulk kernel: plain, or non-temporal for a large
+// source, which is read exactly once and would otherwise sweep the cache
+// the accumulator's read-modify-write lives in.
+template <bool NT>
+__device__ __forceinline__ u32x4 accum_src(const u32x4* p) {
+  if constexpr (NT) return __builtin_nontemporal_load(p);
+  else return *p;
+}
+
+// 16B-vector bulk accumulate (both pointers 16B-aligned). The destination
+// is read-modify-write and stays plain.
+template <class A, bool NT>
+__global__ __launch_bounds__(256) void k_accum_b128(
+    const u32x4* __restrict__ src, u32x4* __restrict__ dst, size_t n16) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  // 4 + 4 independent loads in flight per thread per iteration.
+  while (i + 3 * stride < n16) {
+    u32x4 s0 = accum_src<NT>(&src[i]);
+    u32x4 s1 = accum_src<NT>(&src[i + stride]);
+    u32x4 s2 = accum_src<NT>(&src[i + 2 * stride]);
+    u32x4 s3 = accum_src<NT>(&src[i + 3 * stride]);
+    u32x4 d0 = dst[i];
+    u32x4 d1 = dst[i + stride];
+    u32x4 d2 = dst[i + 2 * stride];
+    u32x4 d3 = dst[i + 3 * stride];
+    dst[i] = accum16<A>(d0, s0);
+    dst[i + stride] = accum16<A>(d1, s1);
+    dst[i + 2 * stride] = accum16<A>(d2, s2);
+    dst[i + 3 * stride] = accum16<A>(d3, s3);
+    i += 4 * stride;
+  }
+  for (; i < n16; i += stride)
+    dst[i] = accum16<A>(dst[i], accum_src<NT>(&src[i]));
+}
+
+// Element-granularity accumulate: heads, tails and pairs that are not 16B
+// co-aligned. Both pointers are element-aligned.
+template <class A>
+__global__ __launch_bounds__(256) void k_accum_elem(
+    const typename A::W* __restrict__ src, typename A::W* __restrict__ dst,
+    size_t n) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) dst[i] = A::add(dst[i], src[i]);
+}
+
+template <class A>
+static hipError_t launch_accum_t(void* dst, const void* src, size_t bytes,
+                                 hipStream_t stream, const CopyTuning& t) {
+  using W = typename A::W;
+  const size_t cap = t.block_cap;
+  uintptr_t s = (uintptr_t)src, d = (uintptr_t)dst;
+  if ((s & 15) == (d & 15)) {
+    // Co-aligned: element head to the next 16B boundary, vector bulk,
+    // element tail. 16 is a multiple of the element size, so head and tail
+    // are whole elements.
+    size_t head = (16 - (s & 15)) & 15;
+    if (head > bytes) head = bytes;
+    if (head) {
+      hipLaunchKernelGGL(k_accum_elem<A>, dim3(1), dim3(64), 0, stream,
+                         (const W*)s, (W*)d, head / sizeof(W));
+      s += head;
+      d += head;
+      bytes -= head;
+    }
+    const size_t n16 = bytes / 16;
+    const size_t tail = bytes & 15;
+    if (n16) {
+      const dim3 grid(copy_grid(n16 / 4 + 1, cap));
+      // Non-temporal source loads from accum_nt_threshold, a knob of the
+      // accumulate family's own: its crossover lies far above the copy
+      // family's nt_threshold (see kAccumNtDefaultThreshold).
+      if (bytes >= t.accum_nt_threshold)
+        hipLaunchKernelGGL((k_accum_b128<A, true>), grid, dim3(256), 0,
+                           stream, (const u32x4*)s, (u32x4*)d, n16);
+      else
+        hipLaunchKernelGGL((k_accum_b128<A, false>), grid, dim3(256), 0,
+                           stream, (const u32x4*)s, (u32x4*)d, n16);
+    }
+    if (tail)
+      hipLaunchKernelGGL(k_accum_elem<A>, dim3(1), dim3(64), 0, stream,
+                         (const W*)(s + n16 * 16), (W*)(d + n16 * 16),
+                         tail / sizeof(W));
+  } else {
+    const size_t n = bytes / sizeof(W);
+    hipLaunchKernelGGL(k_accum_elem<A>, dim3(copy_grid(n / 4 + 1, cap)),
+                       dim3(256), 0, stream, (const W*)s, (W*)d, n);
+  }
+  return hipGetLastError();
+}
+
+// dst and src must be aligned to the element size and `bytes` a multiple
+// of it (the callers in gpu.cpp guarantee both); src must not overlap dst.
+hipError_t launch_accum_tuned(void* dst, const void* src, size_t bytes,
+                              ElemType dtype, hipStream_t stream,
+                              const CopyTuning& t) {
+  const size_t es = elem_size(dtype);
+  if (es == 0 || bytes % es || ((uintptr_t)dst | (uintptr_t)src) % es)
+    return hipErrorInvalidValue;
+  if (bytes == 0) return hipSuccess;
+  switch (dtype) {
+    case ElemType::F32: return launch_accum_t<AccF32>(dst, src, bytes, stream, t);
+    case ElemType::I32: return launch_accum_t<AccI32>(dst, src, bytes, stream, t);
+    case ElemType::F16: return launch_accum_t<AccF16>(dst, src, bytes, stream, t);
+    case ElemType::BF16:
+      return launch_accum_t<AccBF16>(dst, src, bytes, stream, t);
+    case ElemType::None: break;
+  }
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_accum(void* dst, const void* src, size_t bytes,
+                        ElemType dtype, hipStream_t stream) {
+  return launch_accum_tuned(dst, src, bytes, dtype, stream,
+                            default_copy_tuning());
 }
 
 }  // namespace sw

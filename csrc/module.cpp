@@ -106,6 +106,45 @@ static BufferRef parse_buffer(py::handle obj, bool writable) {
   return ref;
 }
 
+static ElemType parse_elem_type(const std::string& dtype) {
+  if (dtype == "float32") return ElemType::F32;
+  if (dtype == "float16") return ElemType::F16;
+  if (dtype == "bfloat16") return ElemType::BF16;
+  if (dtype == "int32") return ElemType::I32;
+  return ElemType::None;
+}
+
+// recv(reduce=..., dtype=...). The op is checked before the buffer is
+// looked at; everything else against the parsed buffer. Every refusal is a
+// ValueError naming the limit.
+static void check_reduce_op(const std::string& reduce) {
+  if (!reduce.empty() && reduce != "sum")
+    throw py::value_error("reduce limit: unknown op '" + reduce +
+                          "' (supported: 'sum')");
+}
+
+static void apply_reduce(BufferRef& ref, const std::string& reduce,
+                         const std::string& dtype) {
+  if (reduce.empty()) return;
+  if (ref.device < 0)
+    throw py::value_error(
+        "reduce limit: host buffers are not supported (device tensors only)");
+  const ElemType et = parse_elem_type(dtype);
+  if (et == ElemType::None)
+    throw py::value_error("reduce limit: unsupported dtype '" + dtype +
+                          "' (supported: float32, float16, bfloat16, int32)");
+  if (!ref.dense())
+    throw py::value_error(
+        "reduce limit: the destination must be contiguous (strided and N-D "
+        "views are not supported)");
+  if ((uintptr_t)ref.ptr % elem_size(et))
+    throw py::value_error("reduce limit: the destination must be aligned to "
+                          "its item size (" +
+                          std::to_string(elem_size(et)) + " B)");
+  ref.reduce = ReduceOp::Sum;
+  ref.elem = et;
+}
+
 // (unit, [(extent, stride_bytes), ...]): a Layout as the test hooks see it.
 using Plan = std::pair<uint64_t, std::vector<std::pair<uint64_t, int64_t>>>;
 
@@ -263,13 +302,17 @@ PYBIND11_MODULE(_core, m) {
            py::arg("done_callback"), py::arg("fail_callback"))
       .def("recv",
            [](PyServer& s, py::object buffer, uint64_t tag, uint64_t tag_mask,
-              py::object done, py::object fail) {
+              py::object done, py::object fail, const std::string& reduce,
+              const std::string& dtype) {
+             check_reduce_op(reduce);
              BufferRef ref = parse_buffer(buffer, /*writable=*/true);
+             apply_reduce(ref, reduce, dtype);
              s.engine.recv(ref, tag, tag_mask, std::move(done),
                            std::move(fail), std::move(buffer));
            },
            py::arg("buffer"), py::arg("tag"), py::arg("tag_mask"),
-           py::arg("done_callback"), py::arg("fail_callback"))
+           py::arg("done_callback"), py::arg("fail_callback"),
+           py::arg("reduce") = "", py::arg("dtype") = "")
       .def("flush",
            [](PyServer& s, py::object done, py::object fail) {
              s.engine.flush(std::move(done), std::move(fail));
@@ -300,6 +343,7 @@ PYBIND11_MODULE(_core, m) {
              d["inbox_rx"] = st.inbox_rx.load();
              d["inbox_tx"] = st.inbox_tx.load();
              d["doorbell_rx"] = st.doorbell_rx.load();
+             d["reduce_rx"] = st.reduce_rx.load();
              return d;
            })
       .def("list_clients",
@@ -348,13 +392,17 @@ PYBIND11_MODULE(_core, m) {
            py::arg("fail_callback"))
       .def("recv",
            [](PyClient& c, py::object buffer, uint64_t tag, uint64_t tag_mask,
-              py::object done, py::object fail) {
+              py::object done, py::object fail, const std::string& reduce,
+              const std::string& dtype) {
+             check_reduce_op(reduce);
              BufferRef ref = parse_buffer(buffer, /*writable=*/true);
+             apply_reduce(ref, reduce, dtype);
              c.engine.recv(ref, tag, tag_mask, std::move(done),
                            std::move(fail), std::move(buffer));
            },
            py::arg("buffer"), py::arg("tag"), py::arg("tag_mask"),
-           py::arg("done_callback"), py::arg("fail_callback"))
+           py::arg("done_callback"), py::arg("fail_callback"),
+           py::arg("reduce") = "", py::arg("dtype") = "")
       .def("flush",
            [](PyClient& c, py::object done, py::object fail) {
              c.engine.flush(std::move(done), std::move(fail));
@@ -377,6 +425,7 @@ PYBIND11_MODULE(_core, m) {
              d["inbox_rx"] = st.inbox_rx.load();
              d["inbox_tx"] = st.inbox_tx.load();
              d["doorbell_rx"] = st.doorbell_rx.load();
+             d["reduce_rx"] = st.reduce_rx.load();
              return d;
            })
       .def("evaluate_perf", [](PyClient& c, uint64_t msg_size) {
@@ -453,6 +502,35 @@ PYBIND11_MODULE(_core, m) {
         py::arg("dst"), py::arg("dst_stride"), py::arg("src"),
         py::arg("src_stride"), py::arg("rows"), py::arg("row_bytes"),
         py::arg("device"), py::arg("block_cap") = 0);
+  // The accumulate kernels (reducing receive): dst[i] += src[i] over
+  // nbytes / itemsize elements of `dtype` (float32, float16, bfloat16,
+  // int32). Synchronous, on the pull stream, like _copy_device_sync.
+  // nt_threshold is CopyTuning::accum_nt_threshold, not the copies' knob.
+  m.def("_accum_sync",
+        [](uintptr_t dst, uintptr_t src, size_t nbytes,
+           const std::string& dtype, int device, size_t block_cap,
+           size_t nt_threshold) {
+          const ElemType et = parse_elem_type(dtype);
+          if (et == ElemType::None)
+            throw py::value_error("accum_sync: unsupported dtype '" + dtype +
+                                  "'");
+          if (nbytes % elem_size(et) || (dst | src) % elem_size(et))
+            throw py::value_error("accum_sync: pointers and length must be "
+                                  "multiples of the item size");
+          std::string err;
+          bool ok;
+          {
+            py::gil_scoped_release rel;
+            ok = gpu::accum_sync((void*)dst, (const void*)src, nbytes, et,
+                                 device,
+                                 CopyTuning{block_cap, 0, 0, 0, 0, nt_threshold},
+                                 &err);
+          }
+          if (!ok) throw std::runtime_error("accum_sync: " + err);
+        },
+        py::arg("dst"), py::arg("src"), py::arg("nbytes"), py::arg("dtype"),
+        py::arg("device"), py::arg("block_cap") = 0,
+        py::arg("nt_threshold") = 0);
   // descs: list of (dst, src, nbytes); one k_copy_multi launch.
   m.def("_copy_multi_sync",
         [](const std::vector<std::tuple<uintptr_t, uintptr_t, uint64_t>>&

@@ -182,6 +182,46 @@ def _norm_buffer(buf: Any) -> Any:
     return buf
 
 
+_REDUCE_OPS = ("sum",)
+_REDUCE_DTYPES = ("float32", "float16", "bfloat16", "int32")
+_TYPESTR_DTYPES = {"f4": "float32", "f2": "float16", "i4": "int32"}
+
+
+def _reduce_args(buffer: Any, reduce: str | None) -> dict:
+    """Keyword arguments of the native recv for a reducing receive.
+
+    ``reduce="sum"`` adds the message, read as elements of the buffer's
+    dtype, into the buffer: ``buf[i] = buf[i] + msg[i]`` over the first
+    ``length // itemsize`` elements. float16 and bfloat16 add in fp32 and
+    round once. The buffer must be a contiguous device tensor of float32,
+    float16, bfloat16 or int32, aligned to its item size; each limit is a
+    ValueError here, when the receive is posted. The op is checked first,
+    before the buffer is looked at.
+    """
+    if reduce is None:
+        return {}
+    if reduce not in _REDUCE_OPS:
+        raise ValueError(
+            f"reduce limit: unknown op {reduce!r} (supported: 'sum')")
+    name = None
+    if type(buffer).__module__.startswith("torch"):
+        if not buffer.is_cuda:
+            raise ValueError("reduce limit: host buffers are not supported "
+                             "(device tensors only)")
+        name = str(buffer.dtype).removeprefix("torch.")
+    elif hasattr(buffer, "__cuda_array_interface__"):
+        typestr = buffer.__cuda_array_interface__["typestr"]
+        name = _TYPESTR_DTYPES.get(typestr[1:], typestr)
+    else:
+        raise ValueError("reduce limit: host buffers are not supported "
+                         "(device tensors only)")
+    if name not in _REDUCE_DTYPES:
+        raise ValueError(
+            f"reduce limit: unsupported dtype {name!r} (supported: "
+            f"{', '.join(_REDUCE_DTYPES)})")
+    return {"reduce": reduce, "dtype": name}
+
+
 class Server:
     def __init__(self) -> None:
         self._server = _Server(_context)
@@ -220,9 +260,12 @@ class Server:
             client_ep, _norm_buffer(buffer), tag, done_callback, fail_callback
         )
 
-    def recv(self, buffer, tag, tag_mask, done_callback, fail_callback):
+    def recv(self, buffer, tag, tag_mask, done_callback, fail_callback, *,
+             reduce: str | None = None):
+        kw = _reduce_args(buffer, reduce)
         return self._server.recv(
-            _norm_buffer(buffer), tag, tag_mask, done_callback, fail_callback
+            _norm_buffer(buffer), tag, tag_mask, done_callback, fail_callback,
+            **kw
         )
 
     def flush(self, done_callback, fail_callback):
@@ -249,7 +292,11 @@ class Server:
         return ret
 
     def arecv(self, buffer, tag: int, tag_mask: int,
-              loop: asyncio.AbstractEventLoop | None = None):
+              loop: asyncio.AbstractEventLoop | None = None, *,
+              reduce: str | None = None):
+        """Post a receive. ``reduce="sum"`` makes it a reducing receive
+        (see ``_reduce_args``): the message is added into the buffer."""
+        kw = _reduce_args(buffer, reduce)
         if loop is None:
             loop = asyncio.get_running_loop()
         ret: asyncio.Future[tuple[int, int]] = asyncio.Future(loop=loop)
@@ -260,7 +307,7 @@ class Server:
         def bad(reason: str) -> None:
             _disp(ret.get_loop()).post(_set_exception, ret, reason)
 
-        self._server.recv(_norm_buffer(buffer), tag, tag_mask, ok, bad)
+        self._server.recv(_norm_buffer(buffer), tag, tag_mask, ok, bad, **kw)
         return ret
 
     def aflush(self, loop: asyncio.AbstractEventLoop | None = None):
@@ -351,9 +398,12 @@ class Client:
             _norm_buffer(buffer), tag, done_callback, fail_callback
         )
 
-    def recv(self, buffer, tag, tag_mask, done_callback, fail_callback):
+    def recv(self, buffer, tag, tag_mask, done_callback, fail_callback, *,
+             reduce: str | None = None):
+        kw = _reduce_args(buffer, reduce)
         return self._client.recv(
-            _norm_buffer(buffer), tag, tag_mask, done_callback, fail_callback
+            _norm_buffer(buffer), tag, tag_mask, done_callback, fail_callback,
+            **kw
         )
 
     def flush(self, done_callback, fail_callback):
@@ -377,7 +427,11 @@ class Client:
         return ret
 
     def arecv(self, buffer, tag: int, tag_mask: int,
-              loop: asyncio.AbstractEventLoop | None = None):
+              loop: asyncio.AbstractEventLoop | None = None, *,
+              reduce: str | None = None):
+        """Post a receive. ``reduce="sum"`` makes it a reducing receive
+        (see ``_reduce_args``): the message is added into the buffer."""
+        kw = _reduce_args(buffer, reduce)
         if loop is None:
             loop = asyncio.get_running_loop()
         ret: asyncio.Future[tuple[int, int]] = asyncio.Future(loop=loop)
@@ -388,7 +442,7 @@ class Client:
         def bad(reason: str) -> None:
             _disp(ret.get_loop()).post(_set_exception, ret, reason)
 
-        self._client.recv(_norm_buffer(buffer), tag, tag_mask, ok, bad)
+        self._client.recv(_norm_buffer(buffer), tag, tag_mask, ok, bad, **kw)
         return ret
 
     def aflush(self, loop: asyncio.AbstractEventLoop | None = None):

@@ -46,7 +46,13 @@ class Server:
         tag_mask: int,
         done_callback: Callable[[int, int], None],
         fail_callback: Callable[[str], None],
-    ) -> None: ...
+        reduce: str = "",
+        dtype: str = "",
+    ) -> None:
+        """reduce="sum" with dtype float32 / float16 / bfloat16 / int32: a
+        reducing receive, buf[i] += msg[i] over length // itemsize elements.
+        ValueError for an unknown op, a host buffer, another dtype, a
+        non-contiguous destination or one not aligned to its item size."""
     def flush(
         self, done_callback: Callable[[], None], fail_callback: Callable[[str], None]
     ) -> None: ...
@@ -84,7 +90,13 @@ class Client:
         tag_mask: int,
         done_callback: Callable[[int, int], None],
         fail_callback: Callable[[str], None],
-    ) -> None: ...
+        reduce: str = "",
+        dtype: str = "",
+    ) -> None:
+        """reduce="sum" with dtype float32 / float16 / bfloat16 / int32: a
+        reducing receive, buf[i] += msg[i] over length // itemsize elements.
+        ValueError for an unknown op, a host buffer, another dtype, a
+        non-contiguous destination or one not aligned to its item size."""
     def flush(
         self, done_callback: Callable[[], None], fail_callback: Callable[[str], None]
     ) -> None: ...
@@ -106,6 +118,18 @@ def _copy_strided_sync(
 def _copy_multi_sync(
     descs: list[tuple[int, int, int]], device: int
 ) -> None: ...
+def _accum_sync(
+    dst: int, src: int, nbytes: int, dtype: str, device: int,
+    block_cap: int = 0, nt_threshold: int = 0,
+) -> None:
+    """Run the accumulate kernels (k_accum_b128 / k_accum_elem)
+    synchronously on raw device pointers: dst[i] += src[i] over nbytes //
+    itemsize elements of dtype (float32, float16, bfloat16, int32).
+    nt_threshold is the accumulate family's own (bulk bytes from which the
+    source loads are non-temporal; 0 = the process default, 192 MiB).
+    ValueError for another dtype, or pointers / a length that are not
+    multiples of the item size."""
+
 def _copy_tuning() -> dict[str, int]: ...
 
 # N-D layouts (csrc/layout.hpp). A plan is (unit, [(extent, stride_bytes),
