@@ -31,14 +31,7 @@
 #include <vector>
 
 #include "copy_stream.hpp"
-#include "copy_tuning.hpp"
-
-namespace sw {
-hipError_t launch_copy(void* dst, const void* src, size_t bytes,
-                       hipStream_t stream, bool same_device);
-hipError_t launch_copy_tuned(void* dst, const void* src, size_t bytes,
-                             hipStream_t stream, const CopyTuning& t);
-}  // namespace sw
+#include "kernels.hpp"
 
 #define CHECK(x)                                                    \
   do {                                                              \

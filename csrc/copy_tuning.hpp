@@ -25,6 +25,10 @@ struct CopyTuning {
   size_t accum_nt_threshold = 0;
 };
 
+// Messages per batched small-message copy (k_copy_multi, begin_pull_multi):
+// the size of the kernel's by-value descriptor array.
+constexpr int kMultiMax = 8;
+
 // stream_threshold value that no message reaches: the streaming kernel off.
 constexpr size_t kStreamNever = ~(size_t)0;
 

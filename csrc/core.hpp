@@ -113,6 +113,9 @@ struct RtsDesc {
   // N-D source layout (src_nd.ndim > 0; src_rows is 0 then): any strided
   // view the three fields above cannot express. See layout.hpp.
   Layout src_nd;
+  // One dense run of message bytes at the source (the batched multi-copy
+  // takes nothing else).
+  bool contiguous() const { return src_rows == 0 && src_nd.ndim == 0; }
 };
 #pragma pack(pop)
 
@@ -187,6 +190,12 @@ struct BufferRef {
   // doorbell, takes the bounce path for eager/inbox/CMA deliveries and
   // needs the exact message size.
   bool dense() const { return rows == 0 && nd.ndim == 0; }
+  // Whether a message of `len` bytes fits this receive buffer: not longer
+  // than it, and exactly its size unless it is dense (a strided window
+  // filled in part would smear partial rows).
+  bool accepts(uint64_t len) const {
+    return len <= size && (dense() || len == size);
+  }
   bool reducing() const { return reduce != ReduceOp::None; }
   // Dense, and delivery overwrites: only such a device buffer may be
   // written by a copy that does not go through begin_pull or begin_h2d
@@ -750,9 +759,9 @@ bool make_rts(const BufferRef& buf, RtsDesc* out, std::string* err);
 // source; STARWAY_PULL=sdma does not apply to it.
 void* begin_pull(const RtsDesc& rts, const BufferRef& dst, uint64_t size,
                  std::string* err);
-// Batched small-message pull: one launch + one event for up to 8 messages
-// targeting the same destination device. Each entry must be a contiguous
-// device->device transfer. Returns one shared ticket.
+// Batched small-message pull: one launch + one event for up to kMultiMax
+// messages targeting the same destination device. Each entry must be a
+// contiguous device->device transfer. Returns one shared ticket.
 struct PullReq {
   RtsDesc rts;
   uint8_t* dst_ptr;

@@ -166,8 +166,7 @@ void Engine::complete_recv_from_unexpected(Op* op, UnexpectedMsg* um) {
     deliver_recv(op, um->tag, um->size, RxPlane::None);
     return;
   }
-  if (um->size > op->buf.size ||
-      (op->buf.nd.ndim > 0 && um->size != op->buf.size)) {
+  if (!op->buf.accepts(um->size)) {
     fail_op(op, "receive failed: " + truncated_msg(um->size, op->buf.size));
     return;
   }

@@ -28,30 +28,32 @@ void Engine::handle_rts(Connection* c, const RtsDesc& rts, uint64_t tag,
 
 void Engine::start_gpu_pull(Op* recv_op, const RtsDesc& rts, uint64_t tag,
                             uint64_t size, uint64_t sender_op, Connection* c) {
-  // An N-D window needs the exact message size (a 2-D one too: begin_pull
-  // refuses it with its own geometry text).
-  if (size > recv_op->buf.size ||
-      (recv_op->buf.nd.ndim > 0 && size != recv_op->buf.size)) {
-    reject_rndv(c, sender_op, recv_op, truncated_msg(size, recv_op->buf.size));
+  // A rows window offered a shorter message is let through on purpose:
+  // begin_pull refuses it with its geometry text, which is what callers of
+  // this plane have always seen, not the truncation text.
+  const BufferRef& buf = recv_op->buf;
+  if (!buf.accepts(size) && !(buf.rows > 0 && size < buf.size)) {
+    reject_rndv(c, sender_op, recv_op, truncated_msg(size, buf.size));
     return;
   }
-  if (!recv_op->buf.whole_elems(size)) {
-    reject_rndv(c, sender_op, recv_op, reduce_len_msg(size, recv_op->buf));
+  if (!buf.whole_elems(size)) {
+    reject_rndv(c, sender_op, recv_op, reduce_len_msg(size, buf));
     return;
   }
   // Small contiguous device->device messages are batched: collected here,
   // launched as one multi-copy kernel + one event at the end of the loop
   // iteration (the per-launch cost dominates small-message rate). Never a
   // reducing recv: k_copy_multi overwrites.
-  static const uint64_t kMultiMax = env_u64("STARWAY_MULTI_COPY_MAX", 65536);
-  if (size > 0 && size <= kMultiMax && recv_op->buf.device >= 0 &&
-      recv_op->buf.plain() && rts.src_rows == 0 && rts.src_nd.ndim == 0) {
+  static const uint64_t multi_copy_max =
+      env_u64("STARWAY_MULTI_COPY_MAX", 65536);
+  if (size > 0 && size <= multi_copy_max && buf.device >= 0 && buf.plain() &&
+      rts.contiguous()) {
     pending_small_pulls_.push_back(
         SmallPull{rts, recv_op, c, sender_op, tag, size});
     return;
   }
   std::string err;
-  void* ticket = gpu::begin_pull(rts, recv_op->buf, size, &err);
+  void* ticket = gpu::begin_pull(rts, buf, size, &err);
   if (!ticket) {
     reject_rndv(c, sender_op, recv_op, err);
     return;
@@ -85,14 +87,14 @@ bool Engine::upload_to_recv(Op* r, uint64_t tag, uint64_t len,
 }
 
 void Engine::flush_small_pulls() {
-  // Group by destination device; launch batches of up to 8 per kernel. A
-  // lone pull goes through the ordinary single path.
+  // Group by destination device; launch batches of up to kMultiMax per
+  // kernel. A lone pull goes through the ordinary single path.
   while (!pending_small_pulls_.empty()) {
     int dev = pending_small_pulls_[0].recv_op->buf.device;
-    gpu::PullReq reqs[8];
-    SmallPull items[8];
+    gpu::PullReq reqs[kMultiMax];
+    SmallPull items[kMultiMax];
     int n = 0;
-    for (size_t i = 0; i < pending_small_pulls_.size() && n < 8;) {
+    for (size_t i = 0; i < pending_small_pulls_.size() && n < kMultiMax;) {
       if (pending_small_pulls_[i].recv_op->buf.device == dev) {
         items[n] = pending_small_pulls_[i];
         reqs[n] = gpu::PullReq{items[n].rts, items[n].recv_op->buf.ptr, dev,
@@ -143,7 +145,7 @@ void Engine::inbox_release_seq(Connection* c, uint64_t seq) {
 // dst; the unpack kernel overwrites).
 void Engine::dispatch_smsg_to_recv(Connection* c, Op* r, uint64_t tag,
                                    uint64_t size, uint64_t seq) {
-  if (size > r->buf.size || (!r->buf.dense() && size != r->buf.size)) {
+  if (!r->buf.accepts(size)) {
     fail_op(r, "receive failed: " + truncated_msg(size, r->buf.size));
     inbox_release_seq(c, seq);  // discard without reading the slot
     return;
@@ -498,8 +500,7 @@ void Engine::progress_armed(bool& did_work) {
 void Engine::start_cma_pull(Op* recv_op, const CmaDesc& cma, uint64_t tag,
                             uint64_t size, uint64_t sender_op,
                             Connection* c) {
-  if (size > recv_op->buf.size ||
-      (!recv_op->buf.dense() && size != recv_op->buf.size)) {
+  if (!recv_op->buf.accepts(size)) {
     reject_rndv(c, sender_op, recv_op, truncated_msg(size, recv_op->buf.size));
     return;
   }

@@ -881,9 +881,7 @@ void Engine::begin_eager(Connection* c) {
   // Match against posted recvs in FIFO order.
   if (Op* r = take_matching_recv(tag)) {
     {
-      if (msg_len > r->buf.size ||
-          (!r->buf.dense() && msg_len != r->buf.size) ||
-          !r->buf.whole_elems(msg_len)) {
+      if (!r->buf.accepts(msg_len) || !r->buf.whole_elems(msg_len)) {
         // Truncation / strided-geometry mismatch / a reducing recv offered
         // part of an element: consume + fail
         // (UCX MESSAGE_TRUNCATED analog; a strided window needs the exact
@@ -951,9 +949,7 @@ void Engine::finish_eager_into_recv(Connection* c) {
     if (c->rx_truncated) {
       c->rx_truncated = false;
       // Same order as every other plane: too long first.
-      const bool fits =
-          r->recv_len <= r->buf.size &&
-          (r->buf.dense() || r->recv_len == r->buf.size);
+      const bool fits = r->buf.accepts(r->recv_len);
       fail_op(r, "receive failed: " +
                      (fits ? reduce_len_msg(r->recv_len, r->buf)
                            : truncated_msg(r->recv_len, r->buf.size)));

@@ -8,6 +8,8 @@
 //   * completion = hipEvent recorded on the pull stream, polled by the
 //     engine's progress loop (the ucp_worker_progress analog)
 #include "core.hpp"
+#include "gpu_internal.hpp"
+#include "kernels.hpp"
 
 #include <dlfcn.h>
 #include <sys/stat.h>
@@ -19,47 +21,6 @@
 #include <tuple>
 
 namespace sw {
-// kernels.hip
-struct MultiCopyDesc {
-  const uint8_t* src;
-  uint8_t* dst;
-  uint32_t bytes;
-};
-hipError_t launch_copy_multi(const MultiCopyDesc* descs, int n,
-                             hipStream_t stream);
-// same_device: src and dst live on the GPU that runs the kernel. Only then
-// may the copy take the streaming route (see launch_copy in kernels.hip).
-hipError_t launch_copy(void* dst, const void* src, size_t bytes,
-                       hipStream_t stream, bool same_device);
-int copy_stream_unroll();
-hipError_t launch_copy_strided(void* dst, uint64_t dst_stride,
-                               const void* src, uint64_t src_stride,
-                               uint64_t rows, uint64_t row_bytes,
-                               hipStream_t stream);
-hipError_t launch_copy_tuned(void* dst, const void* src, size_t bytes,
-                             hipStream_t stream, const CopyTuning& t);
-hipError_t launch_copy_strided_tuned(void* dst, uint64_t dst_stride,
-                                     const void* src, uint64_t src_stride,
-                                     uint64_t rows, uint64_t row_bytes,
-                                     hipStream_t stream, const CopyTuning& t);
-hipError_t launch_copy_nd(void* dst, const Layout& dst_layout,
-                          const void* src, const Layout& src_layout,
-                          uint64_t bytes, hipStream_t stream);
-hipError_t launch_copy_nd_tuned(void* dst, const Layout& dst_layout,
-                                const void* src, const Layout& src_layout,
-                                uint64_t bytes, hipStream_t stream,
-                                const CopyTuning& t, CopyNdPath path);
-int copy_nd_tile_extent(int elem_bytes);
-// dst[i] += src[i]; both pointers aligned to the element size, bytes a
-// multiple of it, no overlap.
-hipError_t launch_accum(void* dst, const void* src, size_t bytes,
-                        ElemType dtype, hipStream_t stream);
-hipError_t launch_accum_tuned(void* dst, const void* src, size_t bytes,
-                              ElemType dtype, hipStream_t stream,
-                              const CopyTuning& t);
-bool copy_nd_tile_eligible(const Layout& src_layout, const Layout& dst_layout,
-                           const void* src, const void* dst);
-
 namespace gpu {
 
 static std::mutex g_mu;
@@ -165,24 +126,24 @@ static void load_calib_locked() {
   if (xgmi > 0) g_calib.xgmi_gbps = xgmi;
 }
 
+static void free_on(int device, void* p) {
+  DeviceGuard on(device);
+  hipFree(p);
+}
+
 // Timed device copy through the production kernel: dst/src on (possibly
 // different) devices, kernel runs on dst_dev (the pull pattern).
 static double timed_copy_gbps(int dst_dev, int src_dev, size_t nbytes) {
-  int prev;
-  hipGetDevice(&prev);
   void* src = nullptr;
   void* dst = nullptr;
-  hipSetDevice(src_dev);
-  if (hipMalloc(&src, nbytes) != hipSuccess) {
-    hipSetDevice(prev);
-    return 0;
+  {
+    DeviceGuard on(src_dev);
+    if (hipMalloc(&src, nbytes) != hipSuccess) return 0;
+    hipMemset(src, 1, nbytes);
   }
-  hipMemset(src, 1, nbytes);
-  hipSetDevice(dst_dev);
+  DeviceGuard on(dst_dev);
   if (hipMalloc(&dst, nbytes) != hipSuccess) {
-    hipSetDevice(src_dev);
-    hipFree(src);
-    hipSetDevice(prev);
+    free_on(src_dev, src);
     return 0;
   }
   if (dst_dev != src_dev) {
@@ -204,9 +165,7 @@ static double timed_copy_gbps(int dst_dev, int src_dev, size_t nbytes) {
   }
   hipStreamDestroy(s);
   hipFree(dst);
-  hipSetDevice(src_dev);
-  hipFree(src);
-  hipSetDevice(prev);
+  free_on(src_dev, src);
   return best;
 }
 
@@ -310,13 +269,10 @@ static hipStream_t pull_stream(int device, int lane = 0) {
   auto key = std::make_pair(device, lane);
   auto it = streams.find(key);
   if (it != streams.end()) return it->second;
-  int prev;
-  hipGetDevice(&prev);
-  hipSetDevice(device);
+  DeviceGuard on(device);
   hipStream_t s;
   if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess)
     s = nullptr;
-  hipSetDevice(prev);
   streams[key] = s;
   return s;
 }
@@ -330,12 +286,9 @@ static void ensure_peer_access(int dst_dev, int src_dev) {
   static std::set<std::pair<int, int>> enabled;  // guarded by g_mu
   auto key = std::make_pair(dst_dev, src_dev);
   if (enabled.count(key)) return;
-  int prev;
-  hipGetDevice(&prev);
-  hipSetDevice(dst_dev);
+  DeviceGuard on(dst_dev);
   hipError_t e = hipDeviceEnablePeerAccess(src_dev, 0);
   (void)e;  // hipErrorPeerAccessAlreadyEnabled is fine
-  hipSetDevice(prev);
   enabled.insert(key);
 }
 
@@ -367,13 +320,10 @@ static std::map<std::pair<int, HandleKey>, void*> g_import_cache;
 void ipc_close_all() {
   std::lock_guard<std::mutex> lk0(g_mu);
   std::lock_guard<std::mutex> lk(g_ipc_mu);
-  int prev = 0;
-  hipGetDevice(&prev);
   for (auto& [key, base] : g_import_cache) {
-    hipSetDevice(key.first);
+    DeviceGuard on(key.first);
     hipIpcCloseMemHandle(base);
   }
-  hipSetDevice(prev);
   g_import_cache.clear();
   g_export_cache.clear();
 }
@@ -394,9 +344,7 @@ bool make_rts(const BufferRef& buf, RtsDesc* out, std::string* err) {
   out->src_stride = buf.stride;
   out->src_nd = buf.nd;
   // Resolve the allocation base for IPC export.
-  int prev;
-  hipGetDevice(&prev);
-  hipSetDevice(buf.device);
+  DeviceGuard on(buf.device);
   hipDeviceptr_t base = 0;
   size_t bsize = 0;
   hipError_t e = hipMemGetAddressRange(&base, &bsize, (hipDeviceptr_t)buf.ptr);
@@ -423,7 +371,6 @@ bool make_rts(const BufferRef& buf, RtsDesc* out, std::string* err) {
       out->offset = (uint64_t)((uintptr_t)buf.ptr - (uintptr_t)base);
     }
   }
-  hipSetDevice(prev);
   // use_ipc==0 is still fine for same-process delivery (raw_ptr path);
   // a cross-process receiver will report the error.
   return true;
@@ -457,30 +404,6 @@ static void drop_staging(void* staging, hipStream_t stream) {
   if (!staging) return;
   hipStreamSynchronize(stream);
   hipFree(staging);
-}
-
-// The source side of a pull as a Layout, checked against the message size
-// (the descriptor comes from the peer).
-static bool rts_layout(const RtsDesc& rts, uint64_t size, Layout* out,
-                       std::string* err) {
-  try {
-    if (rts.src_nd.ndim > 0) {
-      *out = rts.src_nd;
-      if (out->ndim > kMaxDims || out->unit == 0 ||
-          layout_bytes(*out) != size) {
-        *err = "malformed N-D source layout in RTS";
-        return false;
-      }
-    } else if (rts.src_rows > 0) {
-      *out = rows_layout(rts.src_rows, rts.src_row_bytes, rts.src_stride);
-    } else {
-      *out = contiguous_layout(size);
-    }
-  } catch (const std::invalid_argument& e) {
-    *err = e.what();
-    return false;
-  }
-  return true;
 }
 
 // hipEvent pool per device (create/destroy costs ~1-2 us per op).
@@ -517,11 +440,11 @@ void* import_ipc(const uint8_t* handle, int open_device, std::string* err) {
   hipIpcMemHandle_t h;
   memcpy(&h, handle, kIpcHandleBytes);
   void* base = nullptr;
-  int prev;
-  hipGetDevice(&prev);
-  hipSetDevice(open_device);
-  hipError_t e = hipIpcOpenMemHandle(&base, h, hipIpcMemLazyEnablePeerAccess);
-  hipSetDevice(prev);
+  hipError_t e;
+  {
+    DeviceGuard on(open_device);
+    e = hipIpcOpenMemHandle(&base, h, hipIpcMemLazyEnablePeerAccess);
+  }
   if (e != hipSuccess) {
     *err = std::string("hipIpcOpenMemHandle: ") + hipGetErrorString(e);
     return nullptr;
@@ -530,17 +453,96 @@ void* import_ipc(const uint8_t* handle, int open_device, std::string* err) {
   return base;
 }
 
-static void* resolve_src(const RtsDesc& rts, int open_device,
-                         std::string* err) {
-  bool same_proc = memcmp(rts.src_uuid, process_uuid(), 16) == 0;
-  if (same_proc) return (void*)(uintptr_t)rts.raw_ptr;
-  if (!rts.use_ipc) {
-    *err = "peer did not export an IPC handle (cross-process GPU transfer)";
+// The common tail of every begin_*: the work is queued on `stream`; hand out
+// a ticket whose event follows it and that owns `staging`. A failed launch
+// (`launched`) or a failed event releases the staging and returns null.
+static Ticket* finish_ticket(int device, hipStream_t stream, void* staging,
+                             hipError_t launched, const char* launch_what,
+                             const char* event_what, std::string* err) {
+  if (launched != hipSuccess) {
+    drop_staging(staging, stream);
+    *err = std::string(launch_what) + hipGetErrorString(launched);
     return nullptr;
   }
-  void* base = import_ipc(rts.ipc_handle, open_device, err);
-  if (!base) return nullptr;
-  return (uint8_t*)base + rts.offset;
+  Ticket* t = new Ticket();
+  t->device = device;
+  hipError_t e = pool_get_event(device, &t->ev);
+  if (e == hipSuccess) e = hipEventRecord(t->ev, stream);
+  if (e != hipSuccess) {
+    drop_staging(staging, stream);
+    delete t;
+    *err = std::string(event_what) + hipGetErrorString(e);
+    return nullptr;
+  }
+  t->dev_staging = staging;
+  return t;
+}
+
+// A reducing destination takes whole, aligned elements into a dense buffer.
+static bool check_reduce_dst(const BufferRef& dst, uint64_t size,
+                             std::string* err) {
+  const size_t es = elem_size(dst.elem);
+  if (dst.dense() && es != 0 && (uintptr_t)dst.ptr % es == 0 &&
+      size % es == 0 && size <= dst.size)
+    return true;
+  *err = "reduce: destination or message length does not fit the "
+         "element type";
+  return false;
+}
+
+// A strided window (rows or N-D) takes exactly its own size: a shorter
+// message would smear partial rows.
+static bool check_window(const BufferRef& dst, uint64_t size,
+                         std::string* err) {
+  if (dst.dense() || dst.size == size) return true;
+  *err = "strided recv buffer geometry mismatch (buffer " +
+         std::to_string(dst.size) + " B, message " + std::to_string(size) +
+         " B)";
+  return false;
+}
+
+// The source of a pull, decoded once from the peer's descriptor: where it
+// lies in this process (raw pointer or hipIpc mapping on open_device) and
+// its geometry, as a BufferRef of `size` message bytes on rts.device. The
+// descriptor comes from the peer, so the geometry is checked here, for
+// every route: it must describe exactly `size` bytes.
+struct PullSrc {
+  BufferRef buf;
+  bool same_proc = false;
+};
+
+static bool decode_rts(const RtsDesc& rts, uint64_t size, int open_device,
+                       PullSrc* out, std::string* err) {
+  out->same_proc = memcmp(rts.src_uuid, process_uuid(), 16) == 0;
+  BufferRef& s = out->buf;
+  if (out->same_proc) {
+    s.ptr = (uint8_t*)(uintptr_t)rts.raw_ptr;
+  } else if (!rts.use_ipc) {
+    *err = "peer did not export an IPC handle (cross-process GPU transfer)";
+    return false;
+  } else {
+    void* base = import_ipc(rts.ipc_handle, open_device, err);
+    if (!base) return false;
+    s.ptr = (uint8_t*)base + rts.offset;
+  }
+  s.size = size;
+  s.device = rts.device;
+  if (rts.src_nd.ndim > 0) {
+    s.nd = rts.src_nd;
+    if (s.nd.ndim > kMaxDims || s.nd.unit == 0 || layout_bytes(s.nd) != size) {
+      *err = "malformed N-D source layout in RTS";
+      return false;
+    }
+  } else if (rts.src_rows > 0) {
+    if (rts.src_rows * rts.src_row_bytes != size) {
+      *err = "malformed strided source layout in RTS";
+      return false;
+    }
+    s.rows = rts.src_rows;
+    s.row_bytes = rts.src_row_bytes;
+    s.stride = rts.src_stride;
+  }
+  return true;
 }
 
 // First-contact route self-check: one stderr line per (dst device, src
@@ -566,6 +568,136 @@ static void log_route_once(int run_dev, const RtsDesc& rts, bool same_proc,
           rts.use_ipc ? "hipipc" : "raw-ptr", lane, engine);
 }
 
+// Pack a device source of any geometry into fresh contiguous device staging
+// with the copy kernel that serves that geometry, on `stream`.
+static hipError_t pack_to_staging(const BufferRef& src, int run_dev,
+                                  hipStream_t stream, void** staging) {
+  hipError_t e = alloc_staging(src.size, staging);
+  if (e != hipSuccess) return e;
+  if (src.nd.ndim > 0)
+    return launch_copy_nd(*staging, contiguous_layout(src.size), src.ptr,
+                          src.nd, src.size, stream);
+  if (src.rows > 0)
+    return launch_copy_strided(*staging, src.row_bytes, src.ptr, src.stride,
+                               src.rows, src.row_bytes, stream);
+  return launch_copy(*staging, src.ptr, src.size, stream,
+                     src.device == run_dev);
+}
+
+// Fresh device staging filled from `size` host bytes, on `stream`.
+static hipError_t stage_from_host(const void* host_src, uint64_t size,
+                                  hipStream_t stream, void** staging) {
+  hipError_t e = alloc_staging(size, staging);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(*staging, host_src, size, hipMemcpyHostToDevice,
+                       stream);
+  return e;
+}
+
+// Device source -> host memory: a contiguous or rows source is read where
+// it lies, an N-D one is packed into device staging first.
+static hipError_t download(void* host_dst, const BufferRef& src, int run_dev,
+                           hipStream_t stream, void** staging) {
+  if (src.nd.ndim > 0) {
+    hipError_t e = pack_to_staging(src, run_dev, stream, staging);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(host_dst, *staging, src.size, hipMemcpyDeviceToHost,
+                         stream);
+    return e;
+  }
+  if (src.rows > 0)
+    return hipMemcpy2DAsync(host_dst, src.row_bytes, src.ptr, src.stride,
+                            src.row_bytes, src.rows, hipMemcpyDeviceToHost,
+                            stream);
+  return hipMemcpyAsync(host_dst, src.ptr, src.size, hipMemcpyDeviceToHost,
+                        stream);
+}
+
+// dst += source, on `stream`. The accumulate kernel reads an element-
+// aligned contiguous source where it lies (peer memory over xGMI,
+// hipIpc-mapped, or local); a rows, N-D or element-misaligned source is
+// packed into staging first (same stream, so in order).
+static hipError_t accumulate(const BufferRef& dst, const BufferRef& src,
+                             int run_dev, hipStream_t stream,
+                             void** staging) {
+  const void* from = src.ptr;
+  if (!src.dense() || (uintptr_t)src.ptr % elem_size(dst.elem) != 0) {
+    hipError_t e = pack_to_staging(src, run_dev, stream, staging);
+    if (e != hipSuccess) return e;
+    from = *staging;
+  }
+  return launch_accum(dst.ptr, from, src.size, dst.elem, stream);
+}
+
+// One side of an N-D copy of `size` message bytes, as a Layout.
+static Layout layout_of(const BufferRef& buf, uint64_t size) {
+  return buf.dense() ? contiguous_layout(size) : buf.layout();
+}
+
+// The device-to-device copy for a (source, destination) geometry pair, run
+// on the destination's device; dst overwritten. False with *err set when
+// the pair is refused; else *launched is the launch's status.
+//   either side N-D        launch_copy_nd, the other side as a layout
+//   else either side rows  launch_copy_strided; two rows sides must agree
+//   else (flat)            launch_copy, or SDMA under STARWAY_PULL=sdma
+static bool copy_d2d(const BufferRef& dst, const PullSrc& from, uint64_t size,
+                     hipStream_t stream, hipError_t* launched,
+                     std::string* err) {
+  const BufferRef& src = from.buf;
+  // Pull engine selection: gfx950 copy kernel (default) or the SDMA
+  // engines via hipMemcpyPeerAsync/hipMemcpyAsync (STARWAY_PULL=sdma).
+  // SDMA leaves CUs free and can ride dedicated copy engines; the kernel
+  // streams a large same-device message at 6.4 TB/s of HBM traffic
+  // (docs/benchmark.md "Streaming copy") and is the measured-fast default.
+  static const bool use_sdma = [] {
+    const char* v = getenv("STARWAY_PULL");
+    return v && strcmp(v, "sdma") == 0;
+  }();
+  if (src.nd.ndim > 0 || dst.nd.ndim > 0) {
+    // The only geometry requirement is the total size (check_window).
+    Layout sl{}, dl{};
+    try {
+      sl = layout_of(src, size);
+      dl = layout_of(dst, size);
+    } catch (const std::invalid_argument& ex) {
+      *err = ex.what();
+      return false;
+    }
+    *launched = launch_copy_nd(dst.ptr, dl, src.ptr, sl, size, stream);
+  } else if (src.rows > 0 || dst.rows > 0) {
+    // Pack/unpack inside the pull kernel. Row geometry: the source's if it
+    // has one; a rows destination must agree with it. (The N-D kernel
+    // could serve two rows sides that differ; that is not done.)
+    const BufferRef& g = src.rows > 0 ? src : dst;
+    if (dst.rows > 0 && (dst.rows != g.rows || dst.row_bytes != g.row_bytes)) {
+      *err = "strided send/recv row geometry mismatch";
+      return false;
+    }
+    *launched = launch_copy_strided(
+        dst.ptr, dst.rows > 0 ? dst.stride : g.row_bytes, src.ptr,
+        src.rows > 0 ? src.stride : g.row_bytes, g.rows, g.row_bytes, stream);
+  } else if (use_sdma) {
+    if (from.same_proc && src.device != dst.device)
+      *launched = hipMemcpyPeerAsync(dst.ptr, dst.device, src.ptr, src.device,
+                                     size, stream);
+    else
+      *launched = hipMemcpyAsync(dst.ptr, src.ptr, size,
+                                 hipMemcpyDeviceToDevice, stream);
+  } else {
+    // A source on another GPU is an xGMI pull and keeps the grid-stride
+    // kernels: the streaming route was measured same-device only.
+    *launched = launch_copy(dst.ptr, src.ptr, size, stream,
+                            src.device == dst.device);
+  }
+  return true;
+}
+
+// Routes, by destination:
+//   host      download(): D2H copy, 2-D copy for a rows source, N-D source
+//             packed into device staging first
+//   reducing  accumulate(): k_accum_* from the source where it lies, or
+//             from staging (rows, N-D, element-misaligned source)
+//   device    copy_d2d(): one copy kernel (or SDMA) per geometry pair
 void* begin_pull(const RtsDesc& rts, const BufferRef& dst, uint64_t size,
                  std::string* err) {
   RoctxSpan span("starway::pull");
@@ -576,184 +708,40 @@ void* begin_pull(const RtsDesc& rts, const BufferRef& dst, uint64_t size,
   }
   // The device whose context performs the copy: the destination device for
   // device recv buffers, else the sender's device ordinal (same node).
-  int run_dev = dst.device >= 0 ? dst.device : rts.device;
-  void* src = resolve_src(rts, run_dev, err);
-  if (!src) return nullptr;
+  const int run_dev = dst.device >= 0 ? dst.device : rts.device;
+  PullSrc src;
+  if (!decode_rts(rts, size, run_dev, &src, err)) return nullptr;
 
-  int prev;
-  hipGetDevice(&prev);
-  hipSetDevice(run_dev);
+  DeviceGuard on(run_dev);
   // Lane by SOURCE DEVICE: on a real one-process-per-GPU topology the 7
   // peers live on 7 distinct devices => distinct lanes, full overlap
   // across xGMI links. Same-device peers (shared-GPU emulation) share a
   // lane, which also keeps the per-device HSA queue count low there.
-  int lane = rts.device & (stream_lanes() - 1);
   // Every accumulate into one device rides ONE stream, lane 0 (begin_h2d's
   // too), not the per-source-device lane: two read-modify-write kernels on
   // one buffer must never overlap, and any number of reducing receives
   // into the same buffer may be in flight, from any mix of peers.
-  if (dst.reducing()) lane = 0;
+  const int lane = dst.reducing() ? 0 : rts.device & (stream_lanes() - 1);
   hipStream_t stream = pull_stream(run_dev, lane);
-  hipError_t e;
+  hipError_t e = hipSuccess;
   void* staging = nullptr;
-  if (dst.device >= 0 && dst.reducing()) {
-    bool same_proc = memcmp(rts.src_uuid, process_uuid(), 16) == 0;
-    if (same_proc) ensure_peer_access(dst.device, rts.device);
-    log_route_once(run_dev, rts, same_proc, lane, "gfx950_accum");
-    const size_t es = elem_size(dst.elem);
-    if (!dst.dense() || es == 0 || (uintptr_t)dst.ptr % es || size % es ||
-        size > dst.size) {
-      hipSetDevice(prev);
-      *err = "reduce: destination or message length does not fit the "
-             "element type";
-      return nullptr;
-    }
-    const bool packed = rts.src_rows == 0 && rts.src_nd.ndim == 0;
-    if (packed && (uintptr_t)src % es == 0) {
-      // Fast route: the accumulate kernel reads the source where it lies
-      // (peer memory over xGMI, hipIpc-mapped, or local).
-      e = launch_accum(dst.ptr, src, size, dst.elem, stream);
-    } else {
-      // Slow route (rows, N-D or element-misaligned source): pack into
-      // contiguous device staging with the copy kernels, then accumulate
-      // from staging; same stream, so in order.
-      // Staging holds `size` bytes: the peer's geometry must describe
-      // exactly that many.
-      Layout sl{};
-      if (rts.src_nd.ndim > 0 && !rts_layout(rts, size, &sl, err)) {
-        hipSetDevice(prev);
-        return nullptr;
-      }
-      if (rts.src_rows > 0 && rts.src_rows * rts.src_row_bytes != size) {
-        hipSetDevice(prev);
-        *err = "malformed strided source layout in RTS";
-        return nullptr;
-      }
-      e = alloc_staging(size, &staging);
-      if (e == hipSuccess) {
-        if (rts.src_nd.ndim > 0)
-          e = launch_copy_nd(staging, contiguous_layout(size), src, sl, size,
-                             stream);
-        else if (rts.src_rows > 0)
-          e = launch_copy_strided(staging, rts.src_row_bytes, src,
-                                  rts.src_stride, rts.src_rows,
-                                  rts.src_row_bytes, stream);
-        else
-          e = launch_copy(staging, src, size, stream,
-                          rts.device == run_dev);
-      }
-      if (e == hipSuccess)
-        e = launch_accum(dst.ptr, staging, size, dst.elem, stream);
-    }
-  } else if (dst.device >= 0) {
-    bool same_proc = memcmp(rts.src_uuid, process_uuid(), 16) == 0;
-    if (same_proc) ensure_peer_access(dst.device, rts.device);
-    log_route_once(run_dev, rts, same_proc, lane, "gfx950_copy");
-    // Pull engine selection: gfx950 copy kernel (default) or the SDMA
-    // engines via hipMemcpyPeerAsync/hipMemcpyAsync (STARWAY_PULL=sdma).
-    // SDMA leaves CUs free and can ride dedicated copy engines; the kernel
-    // streams a large same-device message at 6.4 TB/s of HBM traffic
-    // (docs/benchmark.md "Streaming copy") and is the measured-fast default.
-    static const bool use_sdma = [] {
-      const char* v = getenv("STARWAY_PULL");
-      return v && strcmp(v, "sdma") == 0;
-    }();
-    bool src_strided = rts.src_rows > 0;
-    bool dst_strided = dst.rows > 0;
-    const bool nd = rts.src_nd.ndim > 0 || dst.nd.ndim > 0;
-    if (!dst.dense() && dst.size != size) {
-      hipSetDevice(prev);
-      *err = "strided recv buffer geometry mismatch (buffer " +
-             std::to_string(dst.size) + " B, message " +
-             std::to_string(size) + " B)";
-      return nullptr;
-    }
-    if (nd) {
-      // Either side N-D: both are expressed as layouts, and the only
-      // geometry requirement is the total size (checked above).
-      Layout sl{}, dl{};
-      bool ok = rts_layout(rts, size, &sl, err);
-      try {
-        if (ok) dl = dst.dense() ? contiguous_layout(size) : dst.layout();
-      } catch (const std::invalid_argument& ex) {
-        *err = ex.what();
-        ok = false;
-      }
-      if (!ok) {
-        hipSetDevice(prev);
-        return nullptr;
-      }
-      e = launch_copy_nd(dst.ptr, dl, src, sl, size, stream);
-    } else if (src_strided || dst_strided) {
-      // Pack/unpack inside the pull kernel. Row geometry: prefer the
-      // source's; a strided dst must agree on row_bytes.
-      uint64_t rows = src_strided ? rts.src_rows : dst.rows;
-      uint64_t row_bytes = src_strided ? rts.src_row_bytes : dst.row_bytes;
-      if (dst_strided && src_strided &&
-          (dst.rows != rows || dst.row_bytes != row_bytes)) {
-        hipSetDevice(prev);
-        *err = "strided send/recv row geometry mismatch";
-        return nullptr;
-      }
-      uint64_t sstride = src_strided ? rts.src_stride : row_bytes;
-      uint64_t dstride = dst_strided ? dst.stride : row_bytes;
-      e = launch_copy_strided(dst.ptr, dstride, src, sstride, rows,
-                              row_bytes, stream);
-    } else if (use_sdma) {
-      if (same_proc && rts.device != dst.device) {
-        e = hipMemcpyPeerAsync(dst.ptr, dst.device, src, rts.device, size,
-                               stream);
-      } else {
-        e = hipMemcpyAsync(dst.ptr, src, size, hipMemcpyDeviceToDevice,
-                           stream);
-      }
-    } else {
-      // A source on another GPU (rts.device != run_dev) is an xGMI pull and
-      // keeps the grid-stride kernels: the streaming route was measured
-      // same-device only.
-      e = launch_copy(dst.ptr, src, size, stream, rts.device == run_dev);
-    }
+  if (dst.device < 0) {
+    e = download(dst.ptr, src.buf, run_dev, stream, &staging);
   } else {
-    if (rts.src_nd.ndim > 0) {
-      Layout sl{};
-      if (!rts_layout(rts, size, &sl, err)) {
-        hipSetDevice(prev);
-        return nullptr;
-      }
-      e = alloc_staging(size, &staging);
-      if (e == hipSuccess)
-        e = launch_copy_nd(staging, contiguous_layout(size), src, sl, size,
-                           stream);
-      if (e == hipSuccess)
-        e = hipMemcpyAsync(dst.ptr, staging, size, hipMemcpyDeviceToHost,
-                           stream);
-    } else if (rts.src_rows > 0) {
-      e = hipMemcpy2DAsync(dst.ptr, rts.src_row_bytes, src, rts.src_stride,
-                           rts.src_row_bytes, rts.src_rows,
-                           hipMemcpyDeviceToHost, stream);
+    if (src.same_proc) ensure_peer_access(dst.device, rts.device);
+    log_route_once(run_dev, rts, src.same_proc, lane,
+                   dst.reducing() ? "gfx950_accum" : "gfx950_copy");
+    if (dst.reducing()) {
+      if (!check_reduce_dst(dst, size, err)) return nullptr;
+      e = accumulate(dst, src.buf, run_dev, stream, &staging);
     } else {
-      e = hipMemcpyAsync(dst.ptr, src, size, hipMemcpyDeviceToHost, stream);
+      if (!check_window(dst, size, err) ||
+          !copy_d2d(dst, src, size, stream, &e, err))
+        return nullptr;
     }
   }
-  if (e != hipSuccess) {
-    drop_staging(staging, stream);
-    hipSetDevice(prev);
-    *err = std::string("pull launch: ") + hipGetErrorString(e);
-    return nullptr;
-  }
-  Ticket* t = new Ticket();
-  t->device = run_dev;
-  t->dev_staging = staging;
-  e = pool_get_event(run_dev, &t->ev);
-  if (e == hipSuccess) e = hipEventRecord(t->ev, stream);
-  hipSetDevice(prev);
-  if (e != hipSuccess) {
-    *err = std::string("event: ") + hipGetErrorString(e);
-    drop_staging(staging, stream);
-    delete t;
-    return nullptr;
-  }
-  return t;
+  return finish_ticket(run_dev, stream, staging, e, "pull launch: ",
+                       "event: ", err);
 }
 
 void* begin_pull_multi(const PullReq* reqs, int n, std::string* err) {
@@ -763,41 +751,25 @@ void* begin_pull_multi(const PullReq* reqs, int n, std::string* err) {
     *err = "no HIP device available in receiver process";
     return nullptr;
   }
-  if (n < 1 || n > 8) {
+  if (n < 1 || n > kMultiMax) {
     *err = "begin_pull_multi: bad batch size";
     return nullptr;
   }
   int run_dev = reqs[0].dst_device;
-  MultiCopyDesc descs[8];
+  MultiCopyDesc descs[kMultiMax];
   for (int i = 0; i < n; i++) {
-    void* src = resolve_src(reqs[i].rts, run_dev, err);
-    if (!src) return nullptr;
-    bool same_proc =
-        memcmp(reqs[i].rts.src_uuid, process_uuid(), 16) == 0;
-    if (same_proc) ensure_peer_access(run_dev, reqs[i].rts.device);
-    log_route_once(run_dev, reqs[i].rts, same_proc, 0, "gfx950_multi");
-    descs[i] = {(const uint8_t*)src, reqs[i].dst_ptr,
-                (uint32_t)reqs[i].size};
+    PullSrc src;
+    if (!decode_rts(reqs[i].rts, reqs[i].size, run_dev, &src, err))
+      return nullptr;
+    if (src.same_proc) ensure_peer_access(run_dev, reqs[i].rts.device);
+    log_route_once(run_dev, reqs[i].rts, src.same_proc, 0, "gfx950_multi");
+    descs[i] = {src.buf.ptr, reqs[i].dst_ptr, (uint32_t)reqs[i].size};
   }
-  int prev;
-  hipGetDevice(&prev);
-  hipSetDevice(run_dev);
+  DeviceGuard on(run_dev);
   hipStream_t stream = pull_stream(run_dev, 0);
   hipError_t e = launch_copy_multi(descs, n, stream);
-  Ticket* t = nullptr;
-  if (e == hipSuccess) {
-    t = new Ticket();
-    t->device = run_dev;
-    e = pool_get_event(run_dev, &t->ev);
-    if (e == hipSuccess) e = hipEventRecord(t->ev, stream);
-  }
-  hipSetDevice(prev);
-  if (e != hipSuccess) {
-    *err = std::string("multi pull: ") + hipGetErrorString(e);
-    delete t;
-    return nullptr;
-  }
-  return t;
+  return finish_ticket(run_dev, stream, nullptr, e, "multi pull: ",
+                       "multi pull: ", err);
 }
 
 void* begin_h2d(const BufferRef& dst, const void* src, uint64_t size,
@@ -807,42 +779,25 @@ void* begin_h2d(const BufferRef& dst, const void* src, uint64_t size,
     *err = "no HIP device available for device recv buffer";
     return nullptr;
   }
-  int prev;
-  hipGetDevice(&prev);
-  hipSetDevice(dst.device);
+  DeviceGuard on(dst.device);
+  // pull_stream(device) is lane 0: the one stream all accumulates into
+  // this device share (see begin_pull).
   hipStream_t stream = pull_stream(dst.device);
-  hipError_t e;
+  hipError_t e = hipSuccess;
   void* staging = nullptr;
   if (dst.reducing()) {
-    // pull_stream(device) is lane 0: the one stream all accumulates into
-    // this device share (see begin_pull).
-    const size_t es = elem_size(dst.elem);
-    if (!dst.dense() || es == 0 || (uintptr_t)dst.ptr % es || size % es ||
-        size > dst.size) {
-      hipSetDevice(prev);
-      *err = "reduce: destination or message length does not fit the "
-             "element type";
-      return nullptr;
-    }
-    e = hipSuccess;
+    if (!check_reduce_dst(dst, size, err)) return nullptr;
     if (size > 0) {
-      e = alloc_staging(size, &staging);
-      if (e == hipSuccess)
-        e = hipMemcpyAsync(staging, src, size, hipMemcpyHostToDevice, stream);
+      e = stage_from_host(src, size, stream, &staging);
       if (e == hipSuccess)
         e = launch_accum(dst.ptr, staging, size, dst.elem, stream);
     }
+  } else if (!check_window(dst, size, err)) {
+    return nullptr;
   } else if (dst.nd.ndim > 0) {
-    if (size != dst.size) {
-      hipSetDevice(prev);
-      *err = "strided recv buffer geometry mismatch (buffer " +
-             std::to_string(dst.size) + " B, message " +
-             std::to_string(size) + " B)";
-      return nullptr;
-    }
-    e = alloc_staging(size, &staging);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(staging, src, size, hipMemcpyHostToDevice, stream);
+    // hipMemcpy2DAsync cannot express an N-D layout: host -> staging ->
+    // k_copy_nd -> destination.
+    e = stage_from_host(src, size, stream, &staging);
     if (e == hipSuccess)
       e = launch_copy_nd(dst.ptr, dst.nd, staging, contiguous_layout(size),
                          size, stream);
@@ -853,22 +808,7 @@ void* begin_h2d(const BufferRef& dst, const void* src, uint64_t size,
   } else {
     e = hipMemcpyAsync(dst.ptr, src, size, hipMemcpyHostToDevice, stream);
   }
-  Ticket* t = nullptr;
-  if (e == hipSuccess) {
-    t = new Ticket();
-    t->device = dst.device;
-    e = pool_get_event(dst.device, &t->ev);
-    if (e == hipSuccess) e = hipEventRecord(t->ev, stream);
-  }
-  if (e == hipSuccess) t->dev_staging = staging;
-  else drop_staging(staging, stream);
-  hipSetDevice(prev);
-  if (e != hipSuccess) {
-    *err = std::string("h2d: ") + hipGetErrorString(e);
-    delete t;
-    return nullptr;
-  }
-  return t;
+  return finish_ticket(dst.device, stream, staging, e, "h2d: ", "h2d: ", err);
 }
 
 void* begin_d2h(void* host_dst, const BufferRef& src, std::string* err) {
@@ -877,44 +817,11 @@ void* begin_d2h(void* host_dst, const BufferRef& src, std::string* err) {
     *err = "no HIP device available";
     return nullptr;
   }
-  int prev;
-  hipGetDevice(&prev);
-  hipSetDevice(src.device);
+  DeviceGuard on(src.device);
   hipStream_t stream = pull_stream(src.device);
-  hipError_t e;
   void* staging = nullptr;
-  if (src.nd.ndim > 0) {
-    e = alloc_staging(src.size, &staging);
-    if (e == hipSuccess)
-      e = launch_copy_nd(staging, contiguous_layout(src.size), src.ptr,
-                         src.nd, src.size, stream);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(host_dst, staging, src.size, hipMemcpyDeviceToHost,
-                         stream);
-  } else if (src.rows > 0) {
-    e = hipMemcpy2DAsync(host_dst, src.row_bytes, src.ptr, src.stride,
-                         src.row_bytes, src.rows, hipMemcpyDeviceToHost,
-                         stream);
-  } else {
-    e = hipMemcpyAsync(host_dst, src.ptr, src.size, hipMemcpyDeviceToHost,
-                       stream);
-  }
-  Ticket* t = nullptr;
-  if (e == hipSuccess) {
-    t = new Ticket();
-    t->device = src.device;
-    e = pool_get_event(src.device, &t->ev);
-    if (e == hipSuccess) e = hipEventRecord(t->ev, stream);
-  }
-  if (e == hipSuccess) t->dev_staging = staging;
-  else drop_staging(staging, stream);
-  hipSetDevice(prev);
-  if (e != hipSuccess) {
-    *err = std::string("d2h: ") + hipGetErrorString(e);
-    delete t;
-    return nullptr;
-  }
-  return t;
+  hipError_t e = download(host_dst, src, src.device, stream, &staging);
+  return finish_ticket(src.device, stream, staging, e, "d2h: ", "d2h: ", err);
 }
 
 void attach_bounce(void* ticket, RawBuf&& bounce) {
@@ -968,13 +875,10 @@ static bool run_sync(int device, std::string* err, Launch launch) {
     return false;
   }
   std::lock_guard<std::mutex> lk(g_mu);
-  int prev;
-  hipGetDevice(&prev);
-  hipSetDevice(device);
+  DeviceGuard on(device);
   hipStream_t stream = pull_stream(device);
   hipError_t e = launch(stream);
   if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  hipSetDevice(prev);
   if (e != hipSuccess) {
     *err = hipGetErrorString(e);
     return false;
@@ -1034,14 +938,14 @@ bool accum_sync(void* dst, const void* src, size_t nbytes, ElemType dtype,
   });
 }
 
-// Callers validate 1 <= n <= 8 and bytes < 2^32 (launch_copy_multi does not).
+// Callers validate 1 <= n <= kMultiMax and bytes < 2^32 (launch_copy_multi does not).
 bool copy_multi_sync(const CopyDesc* descs, int n, int device,
                      std::string* err) {
-  if (n < 1 || n > 8) {
+  if (n < 1 || n > kMultiMax) {
     *err = "copy_multi_sync: bad batch size";
     return false;
   }
-  MultiCopyDesc d[8];
+  MultiCopyDesc d[kMultiMax];
   for (int i = 0; i < n; i++)
     d[i] = {(const uint8_t*)descs[i].src, (uint8_t*)descs[i].dst,
             (uint32_t)descs[i].bytes};
@@ -1054,18 +958,11 @@ void synchronize_all() {
   if (!available()) return;
   std::lock_guard<std::mutex> lk(g_mu);
   int n = cached_device_count();
-  int prev;
-  hipGetDevice(&prev);
   for (int d = 0; d < n; d++) {
-    for (int lane = 0; lane < stream_lanes(); lane++) {
-      hipStream_t s = pull_stream(d, lane);
-      if (s) {
-        hipSetDevice(d);
-        hipStreamSynchronize(s);
-      }
-    }
+    DeviceGuard on(d);
+    for (int lane = 0; lane < stream_lanes(); lane++)
+      if (hipStream_t s = pull_stream(d, lane)) hipStreamSynchronize(s);
   }
-  hipSetDevice(prev);
 }
 
 }  // namespace gpu

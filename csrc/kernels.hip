@@ -29,9 +29,7 @@
 #include <cstdlib>
 
 #include "copy_stream.hpp"
-#include "copy_tuning.hpp"
-#include "elem_type.hpp"
-#include "layout.hpp"
+#include "kernels.hpp"
 
 namespace sw {
 
@@ -173,12 +171,6 @@ __global__ __launch_bounds__(256) void k_copy_strided_b8(
 // sustains 600k msgs/s on host buffers but 85k with one launch+event per
 // device message).
 // ---------------------------------------------------------------------------
-struct MultiCopyDesc {
-  const uint8_t* src;
-  uint8_t* dst;
-  uint32_t bytes;
-};
-constexpr int kMultiMax = 8;
 struct MultiCopyArgs {
   MultiCopyDesc d[kMultiMax];
   int n;

@@ -1,0 +1,69 @@
+// Everything kernels.hip exports: the host-side launchers of the gfx950
+// copy and accumulate kernels. Included by kernels.hip itself, so a
+// declaration that drifts from its definition does not compile.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "copy_tuning.hpp"
+#include "elem_type.hpp"
+#include "layout.hpp"
+
+namespace sw {
+
+// One message of a batched small-message copy (k_copy_multi): up to
+// kMultiMax (copy_tuning.hpp) per launch, one block per message.
+struct MultiCopyDesc {
+  const uint8_t* src;
+  uint8_t* dst;
+  uint32_t bytes;
+};
+// Callers validate 1 <= n <= kMultiMax and bytes < 2^32.
+hipError_t launch_copy_multi(const MultiCopyDesc* descs, int n,
+                             hipStream_t stream);
+
+// same_device: src and dst live on the GPU that runs the kernel. Only then
+// may the copy take the streaming route (see launch_copy in kernels.hip).
+hipError_t launch_copy(void* dst, const void* src, size_t bytes,
+                       hipStream_t stream, bool same_device);
+hipError_t launch_copy_tuned(void* dst, const void* src, size_t bytes,
+                             hipStream_t stream, const CopyTuning& t);
+// Elements per lane per tile (U) of the production streaming kernel.
+int copy_stream_unroll();
+
+hipError_t launch_copy_strided(void* dst, uint64_t dst_stride,
+                               const void* src, uint64_t src_stride,
+                               uint64_t rows, uint64_t row_bytes,
+                               hipStream_t stream);
+hipError_t launch_copy_strided_tuned(void* dst, uint64_t dst_stride,
+                                     const void* src, uint64_t src_stride,
+                                     uint64_t rows, uint64_t row_bytes,
+                                     hipStream_t stream, const CopyTuning& t);
+
+// Both layouts describe `bytes` message bytes.
+hipError_t launch_copy_nd(void* dst, const Layout& dst_layout,
+                          const void* src, const Layout& src_layout,
+                          uint64_t bytes, hipStream_t stream);
+hipError_t launch_copy_nd_tuned(void* dst, const Layout& dst_layout,
+                                const void* src, const Layout& src_layout,
+                                uint64_t bytes, hipStream_t stream,
+                                const CopyTuning& t, CopyNdPath path);
+// Tile extent (elements, both axes) of k_copy_nd_tile per element size; 0
+// for an unsupported size.
+int copy_nd_tile_extent(int elem_bytes);
+// Whether the tiled kernel serves this pair of layouts and pointers.
+bool copy_nd_tile_eligible(const Layout& src_layout, const Layout& dst_layout,
+                           const void* src, const void* dst);
+
+// dst[i] += src[i]; both pointers aligned to the element size, bytes a
+// multiple of it, no overlap.
+hipError_t launch_accum(void* dst, const void* src, size_t bytes,
+                        ElemType dtype, hipStream_t stream);
+hipError_t launch_accum_tuned(void* dst, const void* src, size_t bytes,
+                              ElemType dtype, hipStream_t stream,
+                              const CopyTuning& t);
+
+}  // namespace sw

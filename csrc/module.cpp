@@ -536,9 +536,9 @@ PYBIND11_MODULE(_core, m) {
         [](const std::vector<std::tuple<uintptr_t, uintptr_t, uint64_t>>&
                descs,
            int device) {
-          if (descs.empty() || descs.size() > 8)
+          if (descs.empty() || descs.size() > (size_t)kMultiMax)
             throw py::value_error("copy_multi_sync: need 1..8 descriptors");
-          gpu::CopyDesc d[8];
+          gpu::CopyDesc d[kMultiMax];
           for (size_t i = 0; i < descs.size(); i++) {
             auto [dst, src, nbytes] = descs[i];
             if (nbytes >= (1ull << 32))

@@ -34,6 +34,7 @@
 // subsystem replaces what UCX's eager-short protocol + cuda_copy transport
 // would have done, reference benchmark.md:63-89.)
 #include "core.hpp"
+#include "gpu_internal.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -47,8 +48,6 @@
 
 namespace sw {
 namespace gpu {
-
-void* import_ipc(const uint8_t* handle, int open_device, std::string* err);
 
 static std::mutex sm_mu;
 
@@ -263,13 +262,10 @@ static hipStream_t sm_stream(int device, SmStream kind, int lane) {
   auto key = std::make_tuple(device, (int)kind, lane & (sm_lanes() - 1));
   auto it = streams.find(key);
   if (it != streams.end()) return it->second;
-  int prev;
-  hipGetDevice(&prev);
-  hipSetDevice(device);
+  DeviceGuard on(device);
   hipStream_t s;
   if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess)
     s = nullptr;
-  hipSetDevice(prev);
   streams[key] = s;
   return s;
 }
@@ -334,33 +330,32 @@ bool inbox_create(InboxInfo* out, int device, std::string* err) {
   // device is always 0 — the ring must land on the device the USER works
   // on (captured at Server/Client construction on the Python thread; one
   // process per GPU in the bench/production topology).
-  int prev = 0;
-  hipGetDevice(&prev);
-  int dev = device >= 0 ? device : prev;
-  if (hipSetDevice(dev) != hipSuccess) {
-    *err = "no HIP device";
-    return false;
-  }
+  const int dev = device >= 0 ? device : current_device();
   static const uint32_t slots = (uint32_t)env_u64("STARWAY_INBOX_SLOTS", 64);
   static const uint32_t payload =
       (uint32_t)env_u64("STARWAY_INBOX_MAX", 4096);
   uint32_t slot_bytes = kInboxHdrBytes + ((payload + 63) & ~63u);
   void* base = nullptr;
-  hipError_t e = hipMalloc(&base, (size_t)slots * slot_bytes);
-  if (e != hipSuccess) {
-    hipSetDevice(prev);
-    *err = std::string("inbox alloc: ") + hipGetErrorString(e);
-    return false;
-  }
-  hipMemset(base, 0, (size_t)slots * slot_bytes);
-  hipDeviceSynchronize();  // seq words must read 0 before the export leaks
   hipIpcMemHandle_t h;
-  e = hipIpcGetMemHandle(&h, base);
-  hipSetDevice(prev);
-  if (e != hipSuccess) {
-    hipFree(base);
-    *err = std::string("inbox export: ") + hipGetErrorString(e);
-    return false;
+  {
+    DeviceGuard on(dev);
+    if (!on.ok()) {
+      *err = "no HIP device";
+      return false;
+    }
+    hipError_t e = hipMalloc(&base, (size_t)slots * slot_bytes);
+    if (e != hipSuccess) {
+      *err = std::string("inbox alloc: ") + hipGetErrorString(e);
+      return false;
+    }
+    hipMemset(base, 0, (size_t)slots * slot_bytes);
+    hipDeviceSynchronize();  // seq words must read 0 before the export leaks
+    e = hipIpcGetMemHandle(&h, base);
+    if (e != hipSuccess) {
+      hipFree(base);
+      *err = std::string("inbox export: ") + hipGetErrorString(e);
+      return false;
+    }
   }
   out->base = (uint64_t)(uintptr_t)base;
   out->device = dev;
@@ -401,11 +396,8 @@ bool inbox_create(InboxInfo* out, int device, std::string* err) {
 
 void inbox_destroy(const InboxInfo& ib) {
   std::lock_guard<std::mutex> lk(sm_mu);
-  int prev;
-  hipGetDevice(&prev);
-  hipSetDevice(ib.device);
+  DeviceGuard on(ib.device);
   hipFree((void*)(uintptr_t)ib.base);
-  hipSetDevice(prev);
 }
 
 // Resolve the peer's inbox base in OUR address space: raw pointer when the
@@ -443,9 +435,7 @@ void* inbox_push(const InboxInfo& peer, bool same_proc, int run_device,
     args.d[i].seq = msgs[i].seq;
     args.d[i].tag = msgs[i].tag;
   }
-  int prev;
-  hipGetDevice(&prev);
-  hipSetDevice(run_device);
+  DeviceGuard on(run_device);
   hipStream_t stream = sm_stream(run_device, SmStream::Push, lane);
   hipLaunchKernelGGL(k_inbox_push, dim3(n), dim3(256), 0, stream, args);
   hipError_t e = hipGetLastError();
@@ -456,7 +446,6 @@ void* inbox_push(const InboxInfo& peer, bool same_proc, int run_device,
     e = sm_event(run_device, &t->ev);
     if (e == hipSuccess) e = hipEventRecord(t->ev, stream);
   }
-  hipSetDevice(prev);
   if (e != hipSuccess) {
     *err = std::string("inbox push: ") + hipGetErrorString(e);
     delete t;
@@ -539,13 +528,10 @@ void* inbox_unpack(const InboxInfo& mine, const UnpackMsg* msgs, int n,
     args.d[i].dst = dst;
     t->bounces.push_back(msgs[i].dst ? nullptr : dst);
   }
-  int prev;
-  hipGetDevice(&prev);
-  hipSetDevice(mine.device);
+  DeviceGuard on(mine.device);
   hipStream_t stream = sm_stream(mine.device, SmStream::Unpack, lane);
   hipLaunchKernelGGL(k_inbox_unpack, dim3(n), dim3(256), 0, stream, args);
   hipError_t e = hipGetLastError();
-  hipSetDevice(prev);
   if (e != hipSuccess) {
     *err = std::string("inbox unpack: ") + hipGetErrorString(e);
     g_bounce_pool.put((uint8_t*)t->results);
@@ -626,13 +612,10 @@ static ArmTicket* arm_prepare(const InboxInfo& mine, uint64_t expect_seq,
 static bool arm_launch(ArmTicket* t, const ArmArgs& a, int lane,
                        std::string* err) {
   std::lock_guard<std::mutex> lk(sm_mu);
-  int prev;
-  hipGetDevice(&prev);
-  hipSetDevice(t->device);
+  DeviceGuard on(t->device);
   hipStream_t stream = sm_stream(t->device, SmStream::Wait, lane);
   hipLaunchKernelGGL(k_inbox_wait, dim3(1), dim3(256), 0, stream, a);
   hipError_t e = hipGetLastError();
-  hipSetDevice(prev);
   if (e != hipSuccess) {
     *err = std::string("arm: ") + hipGetErrorString(e);
     g_flag_pool.put((uint8_t*)t->result);
@@ -698,11 +681,9 @@ constexpr long kHookDeadlineMs = 2000;
 static bool ring_copy(const InboxInfo& ring, void* dst, const void* src,
                       size_t n, hipMemcpyKind kind, const char* what,
                       std::string* err) {
-  int prev = 0;
-  hipGetDevice(&prev);
-  hipError_t e = hipSetDevice(ring.device);
+  DeviceGuard on(ring.device);
+  hipError_t e = on.status();
   if (e == hipSuccess) e = hipMemcpy(dst, src, n, kind);
-  hipSetDevice(prev);
   if (e != hipSuccess) {
     *err = std::string(what) + ": " + hipGetErrorString(e);
     return false;

@@ -551,6 +551,10 @@ async def test_inbox_unexpected_then_posted():
     async with loopback() as (server, client):
         src = torch.arange(1024, dtype=torch.uint8, device="cuda") % 251
         torch.cuda.synchronize()
+        # Settle as in test_inbox_small_roundtrip: a send that beats the
+        # ring's bring-up probe rides the RTS plane instead, and that send
+        # completes only once its recv is posted, which is below.
+        await asyncio.sleep(0.3)
         await client.asend(src, 42)
         await client.aflush()
         await asyncio.sleep(0.05)  # lands unmatched: parked in the slot
