@@ -31,6 +31,7 @@
 
 #include "copy_tuning.hpp"
 #include "elem_type.hpp"
+#include "index.hpp"
 #include "layout.hpp"
 
 namespace py = pybind11;
@@ -42,7 +43,7 @@ namespace sw {
 // ---------------------------------------------------------------------------
 
 constexpr uint32_t kMagic = 0x53574159;  // "SWAY"
-constexpr uint32_t kProtoVersion = 3;  // 3: RtsDesc carries an N-D layout
+constexpr uint32_t kProtoVersion = 4;  // 4: FT_RTS_INDEXED
 
 enum FrameType : uint16_t {
   FT_HELLO = 1,      // payload: PeerInfo blob (both directions on connect)
@@ -62,6 +63,9 @@ enum FrameType : uint16_t {
   FT_INBOX_OFFER = 14,   // payload: gpu::InboxInfo of MY ring (peer pushes)
   FT_INBOX_CREDIT = 15,  // hdr.aux = consumed seq (slots <= aux are free)
   FT_SMSG = 16,          // hdr.tag/aux/op_id = tag / size / ring seq
+  // FT_RTS whose source is pool[idx]: RtsDesc for the pool's base, then
+  // IndexWire and the u32 entries (index.hpp).
+  FT_RTS_INDEXED = 17,
 };
 
 #pragma pack(push, 1)
@@ -113,8 +117,9 @@ struct RtsDesc {
   // N-D source layout (src_nd.ndim > 0; src_rows is 0 then): any strided
   // view the three fields above cannot express. See layout.hpp.
   Layout src_nd;
-  // One dense run of message bytes at the source (the batched multi-copy
-  // takes nothing else).
+  // One dense run of message bytes at the source, as far as this descriptor
+  // says: an FT_RTS_INDEXED source is never one, whatever this returns (the
+  // batched multi-copy takes nothing else).
   bool contiguous() const { return src_rows == 0 && src_nd.ndim == 0; }
 };
 #pragma pack(pop)
@@ -172,6 +177,9 @@ enum class ReduceOp : uint8_t { None = 0, Sum };
 // ptr + r*stride; size == rows*row_bytes.
 // nd.ndim > 0 => N-D strided device buffer (layout.hpp): every view the
 // rows form cannot express; rows is 0 then and size is the message size.
+// index.on() => indexed device buffer (index.hpp): ptr is the pool's base,
+// the message is the slices the list picks, size == count*slice_bytes;
+// rows and nd are unset then.
 struct BufferRef {
   uint8_t* ptr = nullptr;
   size_t size = 0;
@@ -180,6 +188,7 @@ struct BufferRef {
   uint64_t row_bytes = 0;
   uint64_t stride = 0;
   Layout nd{};
+  IndexRef index{};
   // Reducing receive (recv side only): delivery adds the message, read as
   // elements of `elem`, into the buffer instead of overwriting it. Set only
   // on a dense device buffer whose ptr is aligned to the element size.
@@ -189,7 +198,7 @@ struct BufferRef {
   // unpacked by a copy kernel: it stays off the inbox push plane and the
   // doorbell, takes the bounce path for eager/inbox/CMA deliveries and
   // needs the exact message size.
-  bool dense() const { return rows == 0 && nd.ndim == 0; }
+  bool dense() const { return rows == 0 && nd.ndim == 0 && !index.on(); }
   // Whether a message of `len` bytes fits this receive buffer: not longer
   // than it, and exactly its size unless it is dense (a strided window
   // filled in part would smear partial rows).
@@ -206,7 +215,8 @@ struct BufferRef {
   bool whole_elems(uint64_t len) const {
     return !reducing() || len % elem_size(elem) == 0;
   }
-  // This buffer as a Layout, for a copy whose other side is N-D.
+  // This buffer as a Layout, for a copy whose other side is N-D. Never
+  // asked of an indexed buffer: no Layout describes one.
   Layout layout() const {
     if (nd.ndim > 0) return nd;
     if (rows > 0) return rows_layout(rows, row_bytes, stride);
@@ -335,6 +345,7 @@ struct UnexpectedMsg {
   uint64_t smsg_seq = 0;
   uint64_t sender_op_id = 0;
   RtsDesc rts{};
+  IndexRef rts_index{};  // FT_RTS_INDEXED: the source's index list
   CmaDesc cma{};
   RawBuf data;  // eager staging (uninitialized alloc)
   uint64_t staged = 0;  // bytes counted against the conn's unexpected cap
@@ -482,6 +493,8 @@ class Engine {
     std::atomic<uint64_t> doorbell_rx{0};            // of inbox_rx, pre-armed
     // Delivered reducing receives; each also counts on its plane.
     std::atomic<uint64_t> reduce_rx{0};
+    // Messages sent from / delivered into an indexed buffer.
+    std::atomic<uint64_t> index_tx{0}, index_rx{0};
     std::atomic<uint64_t> unexpected_rx{0};
     std::atomic<uint64_t> unexp_staged_bytes{0};  // flow-control watermark
     std::atomic<uint64_t> deferred_sends{0};      // window-queued sends
@@ -510,10 +523,12 @@ class Engine {
   void on_frame_payload(Connection* c);   // payload fully staged in rx_small
   void begin_eager(Connection* c);
   void finish_eager_into_recv(Connection* c);
-  void handle_rts(Connection* c, const RtsDesc& rts, uint64_t tag,
-                  uint64_t size, uint64_t sender_op);
-  void start_gpu_pull(Op* recv_op, const RtsDesc& rts, uint64_t tag,
-                      uint64_t size, uint64_t sender_op, Connection* c);
+  // src_index: the source's index list (FT_RTS_INDEXED), off otherwise.
+  void handle_rts(Connection* c, const RtsDesc& rts, const IndexRef& src_index,
+                  uint64_t tag, uint64_t size, uint64_t sender_op);
+  void start_gpu_pull(Op* recv_op, const RtsDesc& rts,
+                      const IndexRef& src_index, uint64_t tag, uint64_t size,
+                      uint64_t sender_op, Connection* c);
   void start_cma_pull(Op* recv_op, const CmaDesc& cma, uint64_t tag,
                       uint64_t size, uint64_t sender_op, Connection* c);
   void progress_cma(bool& did_work);
@@ -756,9 +771,11 @@ bool make_rts(const BufferRef& buf, RtsDesc* out, std::string* err);
 // Begin an async pull of `size` bytes described by `rts` into dst (host or
 // device). Returns an opaque ticket (hipEvent) or null on error. A reducing
 // dst is accumulated into (k_accum_*), on lane 0 of its device whatever the
-// source; STARWAY_PULL=sdma does not apply to it.
-void* begin_pull(const RtsDesc& rts, const BufferRef& dst, uint64_t size,
-                 std::string* err);
+// source; STARWAY_PULL=sdma does not apply to it. src_index is the source's
+// index list when the descriptor came in an FT_RTS_INDEXED frame (rts then
+// describes the pool's base), off otherwise.
+void* begin_pull(const RtsDesc& rts, const IndexRef& src_index,
+                 const BufferRef& dst, uint64_t size, std::string* err);
 // Batched small-message pull: one launch + one event for up to kMultiMax
 // messages targeting the same destination device. Each entry must be a
 // contiguous device->device transfer. Returns one shared ticket.
@@ -853,6 +870,12 @@ bool copy_nd_sync(void* dst, const Layout& dst_layout, const void* src,
 // Tile extent (elements, both axes) of k_copy_nd_tile per element size;
 // a compile-time constant of the kernels, 0 for an unsupported size.
 int copy_nd_tile_extent(int elem_bytes);
+// Indexed copy (k_copy_indexed) of `bytes` message bytes. A side whose list
+// is off is one dense run; at least one side is indexed. The lists are
+// uploaded on the pull stream ahead of the kernel, as in production.
+bool copy_index_sync(void* dst, const IndexRef& dst_index, const void* src,
+                     const IndexRef& src_index, uint64_t bytes, int device,
+                     size_t block_cap, std::string* err);
 struct CopyDesc {
   void* dst;
   const void* src;

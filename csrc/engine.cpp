@@ -523,6 +523,8 @@ void Engine::process_command(Op* op) {
 // the wire, captured into engine memory, or (GPU rendezvous) delivery is
 // tracked to RECV_DONE. Delivery is only guaranteed after flush.
 void Engine::start_send(Op* op, Connection* c) {
+  if (op->buf.index.on())
+    stats_.index_tx.fetch_add(1, std::memory_order_relaxed);
   if (cma_eligible(op, c)) {
     CmaDesc desc{};
     desc.pid = (uint64_t)getpid();
@@ -618,8 +620,15 @@ void Engine::start_send(Op* op, Connection* c) {
       fail_op(op, "send failed: " + err);
       return;
     }
-    enqueue_frame(c, FT_RTS, op->tag, op->id, op->buf.size, &rts,
-                  sizeof(rts), /*priority=*/false);
+    if (op->buf.index.on()) {
+      const std::vector<uint8_t> payload =
+          encode_rts_indexed(&rts, sizeof(rts), op->buf.index);
+      enqueue_frame(c, FT_RTS_INDEXED, op->tag, op->id, op->buf.size,
+                    payload.data(), payload.size(), /*priority=*/false);
+    } else {
+      enqueue_frame(c, FT_RTS, op->tag, op->id, op->buf.size, &rts,
+                    sizeof(rts), /*priority=*/false);
+    }
     op->gpu_send_awaiting_ack = true;
     gpu_sends_[op->id] = op;
     c->inflight_rndv_bytes += op->buf.size;
@@ -799,6 +808,8 @@ void Engine::deliver_recv(Op* r, uint64_t tag, uint64_t len, RxPlane plane) {
   }
   if (r->buf.reducing())
     stats_.reduce_rx.fetch_add(1, std::memory_order_relaxed);
+  if (r->buf.index.on() && plane != RxPlane::None)
+    stats_.index_rx.fetch_add(1, std::memory_order_relaxed);
   Completion comp;
   comp.kind = Completion::Kind::RecvDone;
   comp.op = r;

@@ -127,8 +127,8 @@ bool Engine::try_match_unexpected(Op* op) {
     std::unique_ptr<UnexpectedMsg> msg = std::move(*it);
     unexpected_.erase(it);
     if (msg->is_rts)
-      start_gpu_pull(op, msg->rts, msg->tag, msg->size, msg->sender_op_id,
-                     msg->conn);
+      start_gpu_pull(op, msg->rts, msg->rts_index, msg->tag, msg->size,
+                     msg->sender_op_id, msg->conn);
     else if (msg->is_cma)
       start_cma_pull(op, msg->cma, msg->tag, msg->size, msg->sender_op_id,
                      msg->conn);

@@ -15,18 +15,22 @@ static bool debug_arm() {
 
 // ---- GPU rendezvous -------------------------------------------------------
 
-void Engine::handle_rts(Connection* c, const RtsDesc& rts, uint64_t tag,
-                        uint64_t size, uint64_t sender_op) {
+void Engine::handle_rts(Connection* c, const RtsDesc& rts,
+                        const IndexRef& src_index, uint64_t tag, uint64_t size,
+                        uint64_t sender_op) {
   if (Op* r = take_matching_recv(tag)) {
-    start_gpu_pull(r, rts, tag, size, sender_op, c);
+    start_gpu_pull(r, rts, src_index, tag, size, sender_op, c);
     return;
   }
+  // A parked descriptor keeps its index list until the receive is posted.
   UnexpectedMsg* um = park_unexpected(c, tag, size, sender_op);
   um->is_rts = true;
   um->rts = rts;
+  um->rts_index = src_index;
 }
 
-void Engine::start_gpu_pull(Op* recv_op, const RtsDesc& rts, uint64_t tag,
+void Engine::start_gpu_pull(Op* recv_op, const RtsDesc& rts,
+                            const IndexRef& src_index, uint64_t tag,
                             uint64_t size, uint64_t sender_op, Connection* c) {
   // A rows window offered a shorter message is let through on purpose:
   // begin_pull refuses it with its geometry text, which is what callers of
@@ -43,17 +47,18 @@ void Engine::start_gpu_pull(Op* recv_op, const RtsDesc& rts, uint64_t tag,
   // Small contiguous device->device messages are batched: collected here,
   // launched as one multi-copy kernel + one event at the end of the loop
   // iteration (the per-launch cost dominates small-message rate). Never a
-  // reducing recv: k_copy_multi overwrites.
+  // reducing recv: k_copy_multi overwrites. Never an indexed source: its
+  // descriptor alone describes the pool's base, not the message.
   static const uint64_t multi_copy_max =
       env_u64("STARWAY_MULTI_COPY_MAX", 65536);
   if (size > 0 && size <= multi_copy_max && buf.device >= 0 && buf.plain() &&
-      rts.contiguous()) {
+      rts.contiguous() && !src_index.on()) {
     pending_small_pulls_.push_back(
         SmallPull{rts, recv_op, c, sender_op, tag, size});
     return;
   }
   std::string err;
-  void* ticket = gpu::begin_pull(rts, buf, size, &err);
+  void* ticket = gpu::begin_pull(rts, src_index, buf, size, &err);
   if (!ticket) {
     reject_rndv(c, sender_op, recv_op, err);
     return;
@@ -108,8 +113,8 @@ void Engine::flush_small_pulls() {
     std::string err;
     void* ticket = nullptr;
     if (n == 1) {
-      ticket = gpu::begin_pull(items[0].rts, items[0].recv_op->buf,
-                               items[0].size, &err);
+      ticket = gpu::begin_pull(items[0].rts, IndexRef{},
+                               items[0].recv_op->buf, items[0].size, &err);
     } else {
       ticket = gpu::begin_pull_multi(reqs, n, &err);
     }

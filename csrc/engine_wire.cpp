@@ -628,6 +628,7 @@ void Engine::on_frame(Connection* c) {
       return;
     case FT_HELLO:
     case FT_RTS:
+    case FT_RTS_INDEXED:
     case FT_RTS_CPU:
     case FT_RECV_FAIL:
     case FT_SHM_OFFER:
@@ -705,7 +706,23 @@ void Engine::on_frame_payload(Connection* c) {
       }
       RtsDesc rts;
       memcpy(&rts, c->rx_small.data(), sizeof(rts));
-      handle_rts(c, rts, h.tag, h.aux, h.op_id);
+      handle_rts(c, rts, IndexRef{}, h.tag, h.aux, h.op_id);
+      break;
+    }
+    case FT_RTS_INDEXED: {
+      // The descriptor is for the pool's base; the list travels with it as
+      // host bytes, so nothing of the index is read through hipIpc.
+      IndexRef src_index;
+      std::string err;
+      if (!decode_rts_indexed(c->rx_small.data(), c->rx_small.size(),
+                              sizeof(RtsDesc), h.aux, &src_index, &err)) {
+        SW_DBG("%s", err.c_str());
+        on_conn_dead(c);
+        return;
+      }
+      RtsDesc rts;
+      memcpy(&rts, c->rx_small.data(), sizeof(rts));
+      handle_rts(c, rts, src_index, h.tag, h.aux, h.op_id);
       break;
     }
     case FT_RTS_CPU: {
@@ -1000,7 +1017,7 @@ void Engine::enqueue_frame(Connection* c, FrameType t, uint64_t tag,
   h.aux = aux;
   memcpy(item.head.data(), &h, sizeof(h));
   if (payload_len) memcpy(item.head.data() + sizeof(h), payload, payload_len);
-  item.is_data = (t == FT_RTS);
+  item.is_data = (t == FT_RTS || t == FT_RTS_INDEXED);
   item.via_ring = c->shm_tx_enq;
   item.priority = priority;
   c->tx_enqueued_bytes += item.head.size();

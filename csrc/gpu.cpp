@@ -317,6 +317,8 @@ using HandleKey = std::array<uint8_t, kIpcHandleBytes>;
 static std::mutex g_ipc_mu;
 static std::map<std::pair<int, HandleKey>, void*> g_import_cache;
 
+static void release_index_pool();  // g_mu held
+
 void ipc_close_all() {
   std::lock_guard<std::mutex> lk0(g_mu);
   std::lock_guard<std::mutex> lk(g_ipc_mu);
@@ -326,6 +328,9 @@ void ipc_close_all() {
   }
   g_import_cache.clear();
   g_export_cache.clear();
+  // The pooled device index buffers go with the other cached device state
+  // (this runs at interpreter exit too).
+  release_index_pool();
 }
 
 bool make_rts(const BufferRef& buf, RtsDesc* out, std::string* err) {
@@ -380,14 +385,82 @@ bool make_rts(const BufferRef& buf, RtsDesc* out, std::string* err) {
 // tickets
 // ---------------------------------------------------------------------------
 
+// The index lists of one indexed launch on the device: one pooled buffer
+// holding the destination's list, then the source's, filled by
+// hipMemcpyAsync on the route's stream ahead of the kernel. The ticket owns
+// it as it owns staging, and keeps the host lists alive until its event has
+// passed (the async copies read them).
+struct IndexUpload {
+  void* dev = nullptr;
+  size_t cap = 0;
+  int device = -1;
+  std::shared_ptr<const IndexList> host[2];
+};
+
 struct Ticket {
   hipEvent_t ev = nullptr;
   int device = -1;
   RawBuf bounce;  // host staging kept alive until completion
-  // Contiguous device staging of an N-D host<->device transfer; released
-  // with the ticket.
+  // Contiguous device staging of an N-D or indexed transfer; released with
+  // the ticket.
   void* dev_staging = nullptr;
+  IndexUpload index;
 };
+
+// Device index buffers are pooled per device (g_mu held): a list is at most
+// 256 KiB, a message brings at most two, and hipMalloc plus a hipFree that
+// may wait for the device would cost more than a small indexed copy.
+static std::map<int, std::vector<std::pair<void*, size_t>>> g_index_pool;
+
+// A buffer in use is owned by its ticket, not by the pool.
+static void release_index_pool() {
+  for (auto& [device, pool] : g_index_pool) {
+    DeviceGuard on(device);
+    for (auto& buf : pool) hipFree(buf.first);
+  }
+  g_index_pool.clear();
+}
+
+static hipError_t index_buf_get(int device, size_t need, IndexUpload* up) {
+  auto& pool = g_index_pool[device];
+  for (size_t i = 0; i < pool.size(); i++) {
+    if (pool[i].second >= need) {
+      up->dev = pool[i].first;
+      up->cap = pool[i].second;
+      up->device = device;
+      pool.erase(pool.begin() + i);
+      return hipSuccess;
+    }
+  }
+  size_t cap = 4096;
+  while (cap < need) cap <<= 1;
+  hipError_t e = hipMalloc(&up->dev, cap);
+  if (e != hipSuccess) {
+    up->dev = nullptr;
+    return e;
+  }
+  up->cap = cap;
+  up->device = device;
+  return hipSuccess;
+}
+
+// Release staging and index buffer of a route that ends without a ticket;
+// work queued on `stream` may still touch either.
+static void abandon_route(void* staging, IndexUpload* up, hipStream_t stream);
+
+// Hand the buffer back once nothing on the device can still read it:
+// `idle` false means a kernel or copy using it may be in flight, and the
+// buffer is freed (hipFree waits) instead of pooled.
+static void index_buf_put(IndexUpload* up, bool idle) {
+  if (up->dev) {
+    auto& pool = g_index_pool[up->device];
+    if (idle && pool.size() < 16)
+      pool.emplace_back(up->dev, up->cap);
+    else
+      hipFree(up->dev);
+  }
+  *up = IndexUpload{};
+}
 
 // hipMemcpy2DAsync cannot express an N-D layout, so a host endpoint of an
 // N-D device buffer goes through a contiguous device staging buffer on the
@@ -404,6 +477,13 @@ static void drop_staging(void* staging, hipStream_t stream) {
   if (!staging) return;
   hipStreamSynchronize(stream);
   hipFree(staging);
+}
+
+static void abandon_route(void* staging, IndexUpload* up,
+                          hipStream_t stream) {
+  drop_staging(staging, stream);
+  if (up && up->dev)
+    index_buf_put(up, hipStreamSynchronize(stream) == hipSuccess);
 }
 
 // hipEvent pool per device (create/destroy costs ~1-2 us per op).
@@ -457,10 +537,11 @@ void* import_ipc(const uint8_t* handle, int open_device, std::string* err) {
 // a ticket whose event follows it and that owns `staging`. A failed launch
 // (`launched`) or a failed event releases the staging and returns null.
 static Ticket* finish_ticket(int device, hipStream_t stream, void* staging,
-                             hipError_t launched, const char* launch_what,
-                             const char* event_what, std::string* err) {
+                             IndexUpload* index, hipError_t launched,
+                             const char* launch_what, const char* event_what,
+                             std::string* err) {
   if (launched != hipSuccess) {
-    drop_staging(staging, stream);
+    abandon_route(staging, index, stream);
     *err = std::string(launch_what) + hipGetErrorString(launched);
     return nullptr;
   }
@@ -469,12 +550,16 @@ static Ticket* finish_ticket(int device, hipStream_t stream, void* staging,
   hipError_t e = pool_get_event(device, &t->ev);
   if (e == hipSuccess) e = hipEventRecord(t->ev, stream);
   if (e != hipSuccess) {
-    drop_staging(staging, stream);
+    abandon_route(staging, index, stream);
     delete t;
     *err = std::string(event_what) + hipGetErrorString(e);
     return nullptr;
   }
   t->dev_staging = staging;
+  if (index) {
+    t->index = *index;
+    *index = IndexUpload{};
+  }
   return t;
 }
 
@@ -490,8 +575,8 @@ static bool check_reduce_dst(const BufferRef& dst, uint64_t size,
   return false;
 }
 
-// A strided window (rows or N-D) takes exactly its own size: a shorter
-// message would smear partial rows.
+// A strided window (rows or N-D) or an indexed destination takes exactly
+// its own size: a shorter message would smear partial rows or slices.
 static bool check_window(const BufferRef& dst, uint64_t size,
                          std::string* err) {
   if (dst.dense() || dst.size == size) return true;
@@ -511,8 +596,9 @@ struct PullSrc {
   bool same_proc = false;
 };
 
-static bool decode_rts(const RtsDesc& rts, uint64_t size, int open_device,
-                       PullSrc* out, std::string* err) {
+static bool decode_rts(const RtsDesc& rts, const IndexRef& src_index,
+                       uint64_t size, int open_device, PullSrc* out,
+                       std::string* err) {
   out->same_proc = memcmp(rts.src_uuid, process_uuid(), 16) == 0;
   BufferRef& s = out->buf;
   if (out->same_proc) {
@@ -527,7 +613,18 @@ static bool decode_rts(const RtsDesc& rts, uint64_t size, int open_device,
   }
   s.size = size;
   s.device = rts.device;
-  if (rts.src_nd.ndim > 0) {
+  if (src_index.on()) {
+    // The descriptor is for the pool's base; the list came with it in the
+    // frame. The frame decoder has checked it; the sum is checked again
+    // here because every route relies on it.
+    if (src_index.count() * src_index.slice_bytes != size ||
+        src_index.count() > kIndexMax || rts.src_rows > 0 ||
+        rts.src_nd.ndim > 0) {
+      *err = "malformed indexed source in RTS";
+      return false;
+    }
+    s.index = src_index;
+  } else if (rts.src_nd.ndim > 0) {
     s.nd = rts.src_nd;
     if (s.nd.ndim > kMaxDims || s.nd.unit == 0 || layout_bytes(s.nd) != size) {
       *err = "malformed N-D source layout in RTS";
@@ -568,12 +665,51 @@ static void log_route_once(int run_dev, const RtsDesc& rts, bool same_proc,
           rts.use_ipc ? "hipipc" : "raw-ptr", lane, engine);
 }
 
+// One launch of the indexed kernel for `size` message bytes on `stream`,
+// its lists uploaded ahead of it into `up`. A side whose index is off is
+// one dense run; an indexed side's slices must add up to `size`.
+static hipError_t copy_indexed(void* dst, const IndexRef& di, const void* src,
+                               const IndexRef& si, uint64_t size, int run_dev,
+                               hipStream_t stream, const CopyTuning& tuning,
+                               IndexUpload* up) {
+  if ((di.on() && di.count() * di.slice_bytes != size) ||
+      (si.on() && si.count() * si.slice_bytes != size) || up->dev)
+    return hipErrorInvalidValue;
+  if (size == 0) return hipSuccess;
+  const size_t nd = (size_t)di.count() * sizeof(uint32_t);
+  const size_t ns = (size_t)si.count() * sizeof(uint32_t);
+  hipError_t e = index_buf_get(run_dev, nd + ns, up);
+  if (e != hipSuccess) return e;
+  uint8_t* base = (uint8_t*)up->dev;
+  IndexSide d{nullptr, 0, 0}, s{nullptr, 0, 0};
+  if (di.on()) {
+    up->host[0] = di.list;
+    e = hipMemcpyAsync(base, di.list->data(), nd, hipMemcpyHostToDevice,
+                       stream);
+    if (e != hipSuccess) return e;
+    d = IndexSide{(const uint32_t*)base, di.slice_bytes, di.stride};
+  }
+  if (si.on()) {
+    up->host[1] = si.list;
+    e = hipMemcpyAsync(base + nd, si.list->data(), ns, hipMemcpyHostToDevice,
+                       stream);
+    if (e != hipSuccess) return e;
+    s = IndexSide{(const uint32_t*)(base + nd), si.slice_bytes, si.stride};
+  }
+  return launch_copy_indexed_tuned(dst, d, src, s, size, stream, tuning);
+}
+
 // Pack a device source of any geometry into fresh contiguous device staging
-// with the copy kernel that serves that geometry, on `stream`.
+// with the copy kernel that serves that geometry, on `stream`. `up` takes
+// the list of an indexed source.
 static hipError_t pack_to_staging(const BufferRef& src, int run_dev,
-                                  hipStream_t stream, void** staging) {
+                                  hipStream_t stream, void** staging,
+                                  IndexUpload* up) {
   hipError_t e = alloc_staging(src.size, staging);
   if (e != hipSuccess) return e;
+  if (src.index.on())
+    return copy_indexed(*staging, IndexRef{}, src.ptr, src.index, src.size,
+                        run_dev, stream, default_copy_tuning(), up);
   if (src.nd.ndim > 0)
     return launch_copy_nd(*staging, contiguous_layout(src.size), src.ptr,
                           src.nd, src.size, stream);
@@ -595,11 +731,12 @@ static hipError_t stage_from_host(const void* host_src, uint64_t size,
 }
 
 // Device source -> host memory: a contiguous or rows source is read where
-// it lies, an N-D one is packed into device staging first.
+// it lies, an N-D or indexed one is packed into device staging first.
 static hipError_t download(void* host_dst, const BufferRef& src, int run_dev,
-                           hipStream_t stream, void** staging) {
-  if (src.nd.ndim > 0) {
-    hipError_t e = pack_to_staging(src, run_dev, stream, staging);
+                           hipStream_t stream, void** staging,
+                           IndexUpload* up) {
+  if (src.nd.ndim > 0 || src.index.on()) {
+    hipError_t e = pack_to_staging(src, run_dev, stream, staging, up);
     if (e == hipSuccess)
       e = hipMemcpyAsync(host_dst, *staging, src.size, hipMemcpyDeviceToHost,
                          stream);
@@ -615,14 +752,14 @@ static hipError_t download(void* host_dst, const BufferRef& src, int run_dev,
 
 // dst += source, on `stream`. The accumulate kernel reads an element-
 // aligned contiguous source where it lies (peer memory over xGMI,
-// hipIpc-mapped, or local); a rows, N-D or element-misaligned source is
-// packed into staging first (same stream, so in order).
+// hipIpc-mapped, or local); a rows, N-D, indexed or element-misaligned
+// source is packed into staging first (same stream, so in order).
 static hipError_t accumulate(const BufferRef& dst, const BufferRef& src,
-                             int run_dev, hipStream_t stream,
-                             void** staging) {
+                             int run_dev, hipStream_t stream, void** staging,
+                             IndexUpload* up) {
   const void* from = src.ptr;
   if (!src.dense() || (uintptr_t)src.ptr % elem_size(dst.elem) != 0) {
-    hipError_t e = pack_to_staging(src, run_dev, stream, staging);
+    hipError_t e = pack_to_staging(src, run_dev, stream, staging, up);
     if (e != hipSuccess) return e;
     from = *staging;
   }
@@ -637,13 +774,39 @@ static Layout layout_of(const BufferRef& buf, uint64_t size) {
 // The device-to-device copy for a (source, destination) geometry pair, run
 // on the destination's device; dst overwritten. False with *err set when
 // the pair is refused; else *launched is the launch's status.
+//   either side indexed    launch_copy_indexed when the other side is dense
+//                          or indexed too; a rows or N-D side opposite an
+//                          indexed one goes through contiguous staging: the
+//                          source is packed into it by its own kernel, then
+//                          the destination's kernel reads from it
 //   either side N-D        launch_copy_nd, the other side as a layout
 //   else either side rows  launch_copy_strided; two rows sides must agree
 //   else (flat)            launch_copy, or SDMA under STARWAY_PULL=sdma
 static bool copy_d2d(const BufferRef& dst, const PullSrc& from, uint64_t size,
-                     hipStream_t stream, hipError_t* launched,
-                     std::string* err) {
+                     hipStream_t stream, void** staging, IndexUpload* up,
+                     hipError_t* launched, std::string* err) {
   const BufferRef& src = from.buf;
+  if (src.index.on() || dst.index.on()) {
+    const bool src_fits = src.dense() || src.index.on();
+    const bool dst_fits = dst.dense() || dst.index.on();
+    if (src_fits && dst_fits) {
+      *launched = copy_indexed(dst.ptr, dst.index, src.ptr, src.index, size,
+                               dst.device, stream, default_copy_tuning(), up);
+      return true;
+    }
+    *launched = pack_to_staging(src, dst.device, stream, staging, up);
+    if (*launched != hipSuccess) return true;
+    PullSrc staged;
+    staged.same_proc = true;
+    staged.buf.ptr = (uint8_t*)*staging;
+    staged.buf.size = size;
+    staged.buf.device = dst.device;
+    // Dense source now: the next call launches at most one more kernel and
+    // allocates no staging. An indexed source used `up` above, and then the
+    // destination is rows or N-D and needs none; a rows or N-D source did
+    // not, and the indexed destination takes it now.
+    return copy_d2d(dst, staged, size, stream, staging, up, launched, err);
+  }
   // Pull engine selection: gfx950 copy kernel (default) or the SDMA
   // engines via hipMemcpyPeerAsync/hipMemcpyAsync (STARWAY_PULL=sdma).
   // SDMA leaves CUs free and can ride dedicated copy engines; the kernel
@@ -698,8 +861,8 @@ static bool copy_d2d(const BufferRef& dst, const PullSrc& from, uint64_t size,
 //   reducing  accumulate(): k_accum_* from the source where it lies, or
 //             from staging (rows, N-D, element-misaligned source)
 //   device    copy_d2d(): one copy kernel (or SDMA) per geometry pair
-void* begin_pull(const RtsDesc& rts, const BufferRef& dst, uint64_t size,
-                 std::string* err) {
+void* begin_pull(const RtsDesc& rts, const IndexRef& src_index,
+                 const BufferRef& dst, uint64_t size, std::string* err) {
   RoctxSpan span("starway::pull");
   std::lock_guard<std::mutex> lk(g_mu);
   if (!available()) {
@@ -710,7 +873,7 @@ void* begin_pull(const RtsDesc& rts, const BufferRef& dst, uint64_t size,
   // device recv buffers, else the sender's device ordinal (same node).
   const int run_dev = dst.device >= 0 ? dst.device : rts.device;
   PullSrc src;
-  if (!decode_rts(rts, size, run_dev, &src, err)) return nullptr;
+  if (!decode_rts(rts, src_index, size, run_dev, &src, err)) return nullptr;
 
   DeviceGuard on(run_dev);
   // Lane by SOURCE DEVICE: on a real one-process-per-GPU topology the 7
@@ -725,22 +888,26 @@ void* begin_pull(const RtsDesc& rts, const BufferRef& dst, uint64_t size,
   hipStream_t stream = pull_stream(run_dev, lane);
   hipError_t e = hipSuccess;
   void* staging = nullptr;
+  IndexUpload up;
   if (dst.device < 0) {
-    e = download(dst.ptr, src.buf, run_dev, stream, &staging);
+    e = download(dst.ptr, src.buf, run_dev, stream, &staging, &up);
   } else {
     if (src.same_proc) ensure_peer_access(dst.device, rts.device);
     log_route_once(run_dev, rts, src.same_proc, lane,
                    dst.reducing() ? "gfx950_accum" : "gfx950_copy");
     if (dst.reducing()) {
       if (!check_reduce_dst(dst, size, err)) return nullptr;
-      e = accumulate(dst, src.buf, run_dev, stream, &staging);
+      e = accumulate(dst, src.buf, run_dev, stream, &staging, &up);
     } else {
-      if (!check_window(dst, size, err) ||
-          !copy_d2d(dst, src, size, stream, &e, err))
+      if (!check_window(dst, size, err)) return nullptr;
+      if (!copy_d2d(dst, src, size, stream, &staging, &up, &e, err)) {
+        // A pair refused after the source was packed: nothing may leak.
+        abandon_route(staging, &up, stream);
         return nullptr;
+      }
     }
   }
-  return finish_ticket(run_dev, stream, staging, e, "pull launch: ",
+  return finish_ticket(run_dev, stream, staging, &up, e, "pull launch: ",
                        "event: ", err);
 }
 
@@ -759,7 +926,8 @@ void* begin_pull_multi(const PullReq* reqs, int n, std::string* err) {
   MultiCopyDesc descs[kMultiMax];
   for (int i = 0; i < n; i++) {
     PullSrc src;
-    if (!decode_rts(reqs[i].rts, reqs[i].size, run_dev, &src, err))
+    if (!decode_rts(reqs[i].rts, IndexRef{}, reqs[i].size, run_dev, &src,
+                    err))
       return nullptr;
     if (src.same_proc) ensure_peer_access(run_dev, reqs[i].rts.device);
     log_route_once(run_dev, reqs[i].rts, src.same_proc, 0, "gfx950_multi");
@@ -768,7 +936,7 @@ void* begin_pull_multi(const PullReq* reqs, int n, std::string* err) {
   DeviceGuard on(run_dev);
   hipStream_t stream = pull_stream(run_dev, 0);
   hipError_t e = launch_copy_multi(descs, n, stream);
-  return finish_ticket(run_dev, stream, nullptr, e, "multi pull: ",
+  return finish_ticket(run_dev, stream, nullptr, nullptr, e, "multi pull: ",
                        "multi pull: ", err);
 }
 
@@ -785,6 +953,7 @@ void* begin_h2d(const BufferRef& dst, const void* src, uint64_t size,
   hipStream_t stream = pull_stream(dst.device);
   hipError_t e = hipSuccess;
   void* staging = nullptr;
+  IndexUpload up;
   if (dst.reducing()) {
     if (!check_reduce_dst(dst, size, err)) return nullptr;
     if (size > 0) {
@@ -794,6 +963,12 @@ void* begin_h2d(const BufferRef& dst, const void* src, uint64_t size,
     }
   } else if (!check_window(dst, size, err)) {
     return nullptr;
+  } else if (dst.index.on()) {
+    // Host -> staging -> k_copy_indexed -> destination.
+    e = stage_from_host(src, size, stream, &staging);
+    if (e == hipSuccess)
+      e = copy_indexed(dst.ptr, dst.index, staging, IndexRef{}, size,
+                       dst.device, stream, default_copy_tuning(), &up);
   } else if (dst.nd.ndim > 0) {
     // hipMemcpy2DAsync cannot express an N-D layout: host -> staging ->
     // k_copy_nd -> destination.
@@ -808,7 +983,8 @@ void* begin_h2d(const BufferRef& dst, const void* src, uint64_t size,
   } else {
     e = hipMemcpyAsync(dst.ptr, src, size, hipMemcpyHostToDevice, stream);
   }
-  return finish_ticket(dst.device, stream, staging, e, "h2d: ", "h2d: ", err);
+  return finish_ticket(dst.device, stream, staging, &up, e, "h2d: ", "h2d: ",
+                       err);
 }
 
 void* begin_d2h(void* host_dst, const BufferRef& src, std::string* err) {
@@ -820,8 +996,10 @@ void* begin_d2h(void* host_dst, const BufferRef& src, std::string* err) {
   DeviceGuard on(src.device);
   hipStream_t stream = pull_stream(src.device);
   void* staging = nullptr;
-  hipError_t e = download(host_dst, src, src.device, stream, &staging);
-  return finish_ticket(src.device, stream, staging, e, "d2h: ", "d2h: ", err);
+  IndexUpload up;
+  hipError_t e = download(host_dst, src, src.device, stream, &staging, &up);
+  return finish_ticket(src.device, stream, staging, &up, e, "d2h: ", "d2h: ",
+                       err);
 }
 
 void attach_bounce(void* ticket, RawBuf&& bounce) {
@@ -839,9 +1017,13 @@ int poll_ticket(void* ticket, std::string* err) {
 
 void free_ticket(void* ticket) {
   Ticket* t = (Ticket*)ticket;
-  if (t->ev) {
+  {
     std::lock_guard<std::mutex> lk(g_mu);
-    pool_put_event(t->device, t->ev);
+    // A ticket freed before its event has passed (a canceled receive) may
+    // leave its kernel reading the index buffer: not pooled then.
+    if (t->index.dev)
+      index_buf_put(&t->index, t->ev && hipEventQuery(t->ev) == hipSuccess);
+    if (t->ev) pool_put_event(t->device, t->ev);
   }
   if (t->dev_staging) hipFree(t->dev_staging);
   delete t;
@@ -923,6 +1105,23 @@ bool copy_nd_sync(void* dst, const Layout& dst_layout, const void* src,
 
 int copy_nd_tile_extent(int elem_bytes) {
   return sw::copy_nd_tile_extent(elem_bytes);
+}
+
+bool copy_index_sync(void* dst, const IndexRef& dst_index, const void* src,
+                     const IndexRef& src_index, uint64_t bytes, int device,
+                     size_t block_cap, std::string* err) {
+  CopyTuning t = resolve_tuning(CopyTuning{block_cap, 0, 0});
+  IndexUpload up;
+  const bool ok = run_sync(device, err, [&](hipStream_t stream) {
+    return copy_indexed(dst, dst_index, src, src_index, bytes, device, stream,
+                        t, &up);
+  });
+  if (up.dev) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    DeviceGuard on(device);
+    index_buf_put(&up, ok);
+  }
+  return ok;
 }
 
 bool accum_sync(void* dst, const void* src, size_t nbytes, ElemType dtype,

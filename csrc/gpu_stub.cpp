@@ -17,7 +17,7 @@ bool make_rts(const BufferRef&, RtsDesc*, std::string* err) {
   *err = "no GPU (sanitizer stub)";
   return false;
 }
-void* begin_pull(const RtsDesc&, const BufferRef&, uint64_t,
+void* begin_pull(const RtsDesc&, const IndexRef&, const BufferRef&, uint64_t,
                  std::string* err) {
   *err = "no GPU (sanitizer stub)";
   return nullptr;
@@ -58,6 +58,11 @@ bool copy_nd_sync(void*, const Layout&, const void*, const Layout&, uint64_t,
   return false;
 }
 int copy_nd_tile_extent(int) { return 0; }
+bool copy_index_sync(void*, const IndexRef&, const void*, const IndexRef&,
+                     uint64_t, int, size_t, std::string* err) {
+  *err = "no GPU (sanitizer stub)";
+  return false;
+}
 bool copy_multi_sync(const CopyDesc*, int, int, std::string* err) {
   *err = "no GPU (sanitizer stub)";
   return false;

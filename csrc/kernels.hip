@@ -678,6 +678,109 @@ hipError_t launch_copy_nd(void* dst, const Layout& dl, const void* src,
 }
 
 // ---------------------------------------------------------------------------
+// Indexed copy (index.hpp): slices of a pool picked by an index list, on
+// either side or both, e.g. the scattered blocks of a paged KV cache. A side
+// with a null list is one dense run.
+//
+// The shape of k_copy_strided_b128 with a table lookup in place of the row
+// multiply: grid-stride over the message in G-byte granules, in message
+// order, so consecutive lanes take consecutive granules and accesses inside
+// a slice stay coalesced; x4 unroll, no LDS (nothing is reused). Per side
+// and granule one division by the slice length and one 4-byte table load;
+// the lanes of a wave mostly share the quotient, so the load is served as a
+// broadcast out of L1. Both slice sizes are free and independent: slice
+// boundaries of the two sides may interleave.
+//
+// Idx is uint32_t when the host has checked that the granule count (which
+// bounds every quotient and both slice lengths) fits, else uint64_t, as in
+// k_copy_nd. The byte offset idx * stride is 64-bit either way.
+// ---------------------------------------------------------------------------
+
+template <class Idx>
+__device__ __forceinline__ uint64_t indexed_offset(const IndexSide& s, Idx g,
+                                                   Idx slice_g, int shift) {
+  if (s.index == nullptr) return (uint64_t)g << shift;
+  const Idx q = g / slice_g;
+  return (uint64_t)s.index[q] * s.stride + ((uint64_t)(g - q * slice_g) << shift);
+}
+
+template <int G, class Idx>
+__global__ __launch_bounds__(256) void k_copy_indexed(
+    const uint8_t* __restrict__ src, IndexSide ss, uint8_t* __restrict__ dst,
+    IndexSide ds, uint64_t n_granules) {
+  using V = typename GranuleT<G>::type;
+  constexpr int shift = __builtin_ctz(G);
+  // A dense side's slice length is never divided by.
+  const Idx sg = (Idx)(ss.slice_bytes >> shift);
+  const Idx dg = (Idx)(ds.slice_bytes >> shift);
+  const uint64_t n = n_granules;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  // 4 independent granules in flight per thread per iteration.
+  while (i + 3 * stride < n) {
+    V v[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      v[k] = *(const V*)(src + indexed_offset<Idx>(ss, (Idx)(i + k * stride),
+                                                   sg, shift));
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      *(V*)(dst + indexed_offset<Idx>(ds, (Idx)(i + k * stride), dg, shift)) =
+          v[k];
+    i += 4 * stride;
+  }
+  for (; i < n; i += stride)
+    *(V*)(dst + indexed_offset<Idx>(ds, (Idx)i, dg, shift)) =
+        *(const V*)(src + indexed_offset<Idx>(ss, (Idx)i, sg, shift));
+}
+
+template <int G>
+static void launch_indexed(const uint8_t* src, const IndexSide& ss,
+                           uint8_t* dst, const IndexSide& ds, uint64_t bytes,
+                           size_t cap, hipStream_t stream) {
+  const uint64_t n = bytes / G;
+  const dim3 grid(copy_grid(n / 4 + 1, cap));
+  if (n <= UINT32_MAX)
+    hipLaunchKernelGGL((k_copy_indexed<G, uint32_t>), grid, dim3(256), 0,
+                       stream, src, ss, dst, ds, n);
+  else
+    hipLaunchKernelGGL((k_copy_indexed<G, uint64_t>), grid, dim3(256), 0,
+                       stream, src, ss, dst, ds, n);
+}
+
+hipError_t launch_copy_indexed_tuned(void* dst, const IndexSide& ds,
+                                     const void* src, const IndexSide& ss,
+                                     uint64_t bytes, hipStream_t stream,
+                                     const CopyTuning& t) {
+  if (bytes == 0) return hipSuccess;
+  // Two dense sides are launch_copy's; an indexed side has whole, non-empty
+  // slices that add up to the message.
+  if (ds.index == nullptr && ss.index == nullptr) return hipErrorInvalidValue;
+  if ((ds.index && (ds.slice_bytes == 0 || bytes % ds.slice_bytes)) ||
+      (ss.index && (ss.slice_bytes == 0 || bytes % ss.slice_bytes)))
+    return hipErrorInvalidValue;
+  const size_t cap = t.block_cap;
+  const uint8_t* sp = (const uint8_t*)src;
+  uint8_t* dp = (uint8_t*)dst;
+  switch (index_granule((uint64_t)(uintptr_t)dst, ds,
+                        (uint64_t)(uintptr_t)src, ss)) {
+    case 16: launch_indexed<16>(sp, ss, dp, ds, bytes, cap, stream); break;
+    case 8: launch_indexed<8>(sp, ss, dp, ds, bytes, cap, stream); break;
+    case 4: launch_indexed<4>(sp, ss, dp, ds, bytes, cap, stream); break;
+    case 2: launch_indexed<2>(sp, ss, dp, ds, bytes, cap, stream); break;
+    default: launch_indexed<1>(sp, ss, dp, ds, bytes, cap, stream); break;
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_copy_indexed(void* dst, const IndexSide& ds, const void* src,
+                               const IndexSide& ss, uint64_t bytes,
+                               hipStream_t stream) {
+  return launch_copy_indexed_tuned(dst, ds, src, ss, bytes, stream,
+                                   default_copy_tuning());
+}
+
+// ---------------------------------------------------------------------------
 // Accumulate family (reducing receive): dst[i] = dst[i] + src[i]. Same
 // shape as the copy family (256-thread workgroups, 16 B per lane, grid
 // stride, x4 unroll, no LDS: nothing is reused), but the destination is

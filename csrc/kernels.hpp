@@ -10,6 +10,7 @@
 
 #include "copy_tuning.hpp"
 #include "elem_type.hpp"
+#include "index.hpp"
 #include "layout.hpp"
 
 namespace sw {
@@ -57,6 +58,18 @@ int copy_nd_tile_extent(int elem_bytes);
 // Whether the tiled kernel serves this pair of layouts and pointers.
 bool copy_nd_tile_eligible(const Layout& src_layout, const Layout& dst_layout,
                            const void* src, const void* dst);
+
+// Indexed copy (index.hpp) of `bytes` message bytes: message byte m lies at
+// base + index[m / slice_bytes] * stride + m % slice_bytes on a side with a
+// (device) index list and at base + m on a side whose list is null. At
+// least one side is indexed; each indexed side's slices add up to `bytes`.
+hipError_t launch_copy_indexed(void* dst, const IndexSide& dst_side,
+                               const void* src, const IndexSide& src_side,
+                               uint64_t bytes, hipStream_t stream);
+hipError_t launch_copy_indexed_tuned(void* dst, const IndexSide& dst_side,
+                                     const void* src,
+                                     const IndexSide& src_side, uint64_t bytes,
+                                     hipStream_t stream, const CopyTuning& t);
 
 // dst[i] += src[i]; both pointers aligned to the element size, bytes a
 // multiple of it, no overlap.

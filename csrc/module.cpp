@@ -8,7 +8,10 @@
 #include "core.hpp"
 #include "copy_stream.hpp"
 
+#include <algorithm>
+
 #include <pybind11/functional.h>
+#include <pybind11/numpy.h>
 #include <pybind11/stl.h>
 
 namespace sw {
@@ -143,6 +146,180 @@ static void apply_reduce(BufferRef& ref, const std::string& reduce,
                           std::to_string(elem_size(et)) + " B)");
   ref.reduce = ReduceOp::Sum;
   ref.elem = et;
+}
+
+// index= of send/recv: a host-side list of slice numbers along the
+// buffer's first dimension (index.hpp). Every refusal is a ValueError whose
+// text starts with "index limit:".
+static py::value_error index_limit(const std::string& what) {
+  return py::value_error("index limit: " + what);
+}
+
+// Validate and copy an index argument: a sequence of Python ints, a 1-D
+// numpy integer array or a 1-D CPU torch integer tensor.
+static std::shared_ptr<const IndexList> parse_index(py::object index,
+                                                    uint64_t extent,
+                                                    bool writable) {
+  if (py::hasattr(index, "is_cuda")) {  // a torch tensor
+    if (index.attr("is_cuda").cast<bool>())
+      throw index_limit("the index must live on the host (reading a device "
+                        "tensor would need a device synchronise)");
+    index = index.attr("numpy")();
+  } else if (py::hasattr(index, "__cuda_array_interface__")) {
+    throw index_limit("the index must live on the host (reading a device "
+                      "tensor would need a device synchronise)");
+  }
+  std::vector<int64_t> vals;
+  if (py::isinstance<py::array>(index)) {
+    py::array arr = py::reinterpret_borrow<py::array>(index);
+    const char kind = arr.dtype().kind();
+    if (kind != 'i' && kind != 'u')
+      throw index_limit(std::string("the index must hold integers, not ") +
+                        (kind == 'b' ? "bool" : kind == 'f' ? "float"
+                                                            : "this dtype"));
+    if (arr.ndim() != 1)
+      throw index_limit("the index must be 1-D, not " +
+                        std::to_string(arr.ndim()) + "-D");
+    if (kind == 'u' && arr.itemsize() == 8) {
+      // Above int64 is out of range for any buffer; keep it positive.
+      auto u = py::array_t<uint64_t, py::array::c_style |
+                                         py::array::forcecast>(arr);
+      for (ssize_t i = 0; i < u.size(); i++)
+        vals.push_back((int64_t)std::min<uint64_t>(u.data()[i], INT64_MAX));
+    } else {
+      auto a = py::array_t<int64_t, py::array::c_style |
+                                        py::array::forcecast>(arr);
+      vals.assign(a.data(), a.data() + a.size());
+    }
+  } else if (py::isinstance<py::sequence>(index) &&
+             !py::isinstance<py::str>(index) &&
+             !py::isinstance<py::bytes>(index)) {
+    py::sequence seq = py::reinterpret_borrow<py::sequence>(index);
+    for (py::handle h : seq) {
+      if (py::isinstance<py::bool_>(h))
+        throw index_limit("the index must hold integers, not bool");
+      if (py::isinstance<py::float_>(h))
+        throw index_limit("the index must hold integers, not float");
+      if (!py::isinstance<py::int_>(h) && !py::hasattr(h, "__index__"))
+        throw index_limit("the index must be 1-D and hold integers");
+      int overflow = 0;
+      py::object as_int = py::reinterpret_steal<py::object>(
+          PyNumber_Index(h.ptr()));
+      if (!as_int) throw py::error_already_set();
+      long long v = PyLong_AsLongLongAndOverflow(as_int.ptr(), &overflow);
+      if (overflow) v = overflow < 0 ? INT64_MIN : INT64_MAX;
+      vals.push_back((int64_t)v);
+    }
+  } else {
+    throw index_limit("the index must be a sequence of ints, a 1-D numpy "
+                      "integer array or a 1-D CPU torch integer tensor");
+  }
+  return plan_index(vals.data(), vals.size(), extent, writable);
+}
+
+// A message buffer with index=: the device tensor's own geometry (shape and
+// byte strides as they are, not merged), of which the first dimension is
+// indexed and the rest must be dense, so each slice buf[i] is one run.
+static BufferRef parse_indexed_buffer(py::handle obj, py::object index,
+                                      bool writable) {
+  if (!py::hasattr(obj, "__cuda_array_interface__")) {
+    // A host buffer is refused whatever the index; a bad index is still
+    // named first, so its message does not depend on where the buffer is.
+    Py_buffer view;
+    if (PyObject_GetBuffer(obj.ptr(), &view, PyBUF_STRIDES) == 0) {
+      const bool has_dim = view.ndim >= 1;
+      const uint64_t extent = has_dim ? (uint64_t)view.shape[0] : 0;
+      PyBuffer_Release(&view);
+      if (has_dim) parse_index(index, extent, writable);
+    } else {
+      PyErr_Clear();
+    }
+    throw index_limit("host buffers are not supported (device tensors only)");
+  }
+  py::dict cai = obj.attr("__cuda_array_interface__").cast<py::dict>();
+  py::tuple data = cai["data"].cast<py::tuple>();
+  const uintptr_t ptr = data[0].cast<uintptr_t>();
+  if (writable && data[1].cast<bool>())
+    throw std::invalid_argument("recv buffer is read-only");
+  py::tuple shape = cai["shape"].cast<py::tuple>();
+  const std::string typestr = cai["typestr"].cast<std::string>();
+  const uint64_t itemsize = std::stoul(typestr.substr(2));
+  if (shape.size() < 1)
+    throw index_limit("the buffer needs at least one dimension");
+  const uint64_t extent = shape[0].cast<uint64_t>();
+  uint64_t slice_bytes = itemsize;
+  for (size_t i = 1; i < shape.size(); i++)
+    slice_bytes *= shape[i].cast<uint64_t>();
+  uint64_t stride = slice_bytes;
+  if (cai.contains("strides") && !cai["strides"].is_none()) {
+    py::tuple strides = cai["strides"].cast<py::tuple>();
+    uint64_t expect = itemsize;
+    for (ssize_t i = (ssize_t)shape.size() - 1; i >= 1; --i) {
+      const uint64_t extent_i = shape[i].cast<uint64_t>();
+      if (extent_i != 1 && strides[i].cast<int64_t>() != (int64_t)expect)
+        throw index_limit("the buffer's slices must be dense (dimensions "
+                          "after the first contiguous among themselves)");
+      expect *= extent_i;
+    }
+    const int64_t s0 = strides[0].cast<int64_t>();
+    if (s0 < 0)
+      throw index_limit("negative strides are not supported");
+    stride = (uint64_t)s0;
+  }
+  if (writable && extent > 1 && stride < slice_bytes)
+    throw index_limit("a destination's slices must not overlap (stride " +
+                      std::to_string(stride) + " B under a slice of " +
+                      std::to_string(slice_bytes) + " B)");
+  BufferRef ref;
+  ref.index.list = parse_index(std::move(index), extent, writable);
+  // The peer's decoder refuses a list of empty slices as malformed; refuse
+  // it here, where the caller sees why.
+  if (slice_bytes == 0 && ref.index.count() > 0)
+    throw index_limit("the buffer's slices are empty (a dimension after "
+                      "the first has extent 0)");
+  ref.index.slice_bytes = slice_bytes;
+  ref.index.stride = stride;
+  ref.ptr = (uint8_t*)ptr;
+  ref.size = (size_t)(ref.index.count() * slice_bytes);
+  ref.device = gpu::device_of((const void*)ptr);
+  if (ref.device < 0)
+    throw std::invalid_argument(
+        "buffer exports __cuda_array_interface__ but is not resident on a "
+        "visible HIP device");
+  return ref;
+}
+
+// The buffer of a send (reduce empty) or recv, with or without index=.
+static BufferRef parse_message_buffer(py::handle buffer, py::object index,
+                                      bool writable,
+                                      const std::string& reduce = "",
+                                      const std::string& dtype = "") {
+  check_reduce_op(reduce);
+  if (index.is_none()) {
+    BufferRef ref = parse_buffer(buffer, writable);
+    apply_reduce(ref, reduce, dtype);
+    return ref;
+  }
+  if (!reduce.empty())
+    throw index_limit("index= cannot be combined with reduce= (a reducing "
+                      "destination stays contiguous)");
+  return parse_indexed_buffer(buffer, std::move(index), writable);
+}
+
+// One side of _copy_index_sync: None for a dense side.
+static IndexRef hook_index_side(py::object index, uint64_t slice_bytes,
+                                uint64_t stride, bool writable) {
+  IndexRef r;
+  if (index.is_none()) return r;
+  if (slice_bytes == 0 || (writable && stride < slice_bytes))
+    throw py::value_error(std::string("copy_index_sync: bad ") +
+                          (writable ? "destination" : "source") +
+                          " slice size or stride");
+  std::vector<int64_t> v = index.cast<std::vector<int64_t>>();
+  r.list = plan_index(v.data(), v.size(), (uint64_t)UINT32_MAX, writable);
+  r.slice_bytes = slice_bytes;
+  r.stride = stride;
+  return r;
 }
 
 // (unit, [(extent, stride_bytes), ...]): a Layout as the test hooks see it.
@@ -293,26 +470,29 @@ PYBIND11_MODULE(_core, m) {
            py::arg("callback"))
       .def("send",
            [](PyServer& s, std::shared_ptr<EndpointInfo> ep, py::object buffer,
-              uint64_t tag, py::object done, py::object fail) {
-             BufferRef ref = parse_buffer(buffer, /*writable=*/false);
+              uint64_t tag, py::object done, py::object fail,
+              py::object index) {
+             BufferRef ref = parse_message_buffer(buffer, std::move(index),
+                                                  /*writable=*/false);
              s.engine.send(std::move(ep), ref, tag, std::move(done),
                            std::move(fail), std::move(buffer));
            },
            py::arg("client_ep"), py::arg("buffer"), py::arg("tag"),
-           py::arg("done_callback"), py::arg("fail_callback"))
+           py::arg("done_callback"), py::arg("fail_callback"),
+           py::arg("index") = py::none())
       .def("recv",
            [](PyServer& s, py::object buffer, uint64_t tag, uint64_t tag_mask,
               py::object done, py::object fail, const std::string& reduce,
-              const std::string& dtype) {
-             check_reduce_op(reduce);
-             BufferRef ref = parse_buffer(buffer, /*writable=*/true);
-             apply_reduce(ref, reduce, dtype);
+              const std::string& dtype, py::object index) {
+             BufferRef ref = parse_message_buffer(
+                 buffer, std::move(index), /*writable=*/true, reduce, dtype);
              s.engine.recv(ref, tag, tag_mask, std::move(done),
                            std::move(fail), std::move(buffer));
            },
            py::arg("buffer"), py::arg("tag"), py::arg("tag_mask"),
            py::arg("done_callback"), py::arg("fail_callback"),
-           py::arg("reduce") = "", py::arg("dtype") = "")
+           py::arg("reduce") = "", py::arg("dtype") = "",
+           py::arg("index") = py::none())
       .def("flush",
            [](PyServer& s, py::object done, py::object fail) {
              s.engine.flush(std::move(done), std::move(fail));
@@ -344,6 +524,8 @@ PYBIND11_MODULE(_core, m) {
              d["inbox_tx"] = st.inbox_tx.load();
              d["doorbell_rx"] = st.doorbell_rx.load();
              d["reduce_rx"] = st.reduce_rx.load();
+             d["index_tx"] = st.index_tx.load();
+             d["index_rx"] = st.index_rx.load();
              return d;
            })
       .def("list_clients",
@@ -383,26 +565,27 @@ PYBIND11_MODULE(_core, m) {
            py::arg("callback"))
       .def("send",
            [](PyClient& c, py::object buffer, uint64_t tag, py::object done,
-              py::object fail) {
-             BufferRef ref = parse_buffer(buffer, /*writable=*/false);
+              py::object fail, py::object index) {
+             BufferRef ref = parse_message_buffer(buffer, std::move(index),
+                                                  /*writable=*/false);
              c.engine.send(nullptr, ref, tag, std::move(done),
                            std::move(fail), std::move(buffer));
            },
            py::arg("buffer"), py::arg("tag"), py::arg("done_callback"),
-           py::arg("fail_callback"))
+           py::arg("fail_callback"), py::arg("index") = py::none())
       .def("recv",
            [](PyClient& c, py::object buffer, uint64_t tag, uint64_t tag_mask,
               py::object done, py::object fail, const std::string& reduce,
-              const std::string& dtype) {
-             check_reduce_op(reduce);
-             BufferRef ref = parse_buffer(buffer, /*writable=*/true);
-             apply_reduce(ref, reduce, dtype);
+              const std::string& dtype, py::object index) {
+             BufferRef ref = parse_message_buffer(
+                 buffer, std::move(index), /*writable=*/true, reduce, dtype);
              c.engine.recv(ref, tag, tag_mask, std::move(done),
                            std::move(fail), std::move(buffer));
            },
            py::arg("buffer"), py::arg("tag"), py::arg("tag_mask"),
            py::arg("done_callback"), py::arg("fail_callback"),
-           py::arg("reduce") = "", py::arg("dtype") = "")
+           py::arg("reduce") = "", py::arg("dtype") = "",
+           py::arg("index") = py::none())
       .def("flush",
            [](PyClient& c, py::object done, py::object fail) {
              c.engine.flush(std::move(done), std::move(fail));
@@ -426,6 +609,8 @@ PYBIND11_MODULE(_core, m) {
              d["inbox_tx"] = st.inbox_tx.load();
              d["doorbell_rx"] = st.doorbell_rx.load();
              d["reduce_rx"] = st.reduce_rx.load();
+             d["index_tx"] = st.index_tx.load();
+             d["index_rx"] = st.index_rx.load();
              return d;
            })
       .def("evaluate_perf", [](PyClient& c, uint64_t msg_size) {
@@ -609,6 +794,91 @@ PYBIND11_MODULE(_core, m) {
         py::arg("src"), py::arg("src_shape"), py::arg("src_strides"),
         py::arg("itemsize"), py::arg("device"), py::arg("block_cap") = 0,
         py::arg("path") = "auto");
+  // Indexed buffers (index.hpp). _plan_index, _index_offset and the two
+  // descriptor hooks are host-only and work without a GPU.
+  m.attr("_INDEX_MAX") = kIndexMax;
+  m.attr("_RTS_DESC_BYTES") = sizeof(RtsDesc);
+  m.attr("_PROTO_VERSION") = kProtoVersion;
+  m.attr("_FT_RTS_INDEXED") = (int)FT_RTS_INDEXED;
+  m.def("_plan_index",
+        [](py::object index, uint64_t extent, bool writable) {
+          return *parse_index(std::move(index), extent, writable);
+        },
+        py::arg("index"), py::arg("extent"), py::arg("writable") = false);
+  m.def("_index_offset",
+        [](const std::vector<uint32_t>& index, uint64_t slice_bytes,
+           uint64_t stride, uint64_t m) {
+          return index_offset(index, slice_bytes, stride, m);
+        },
+        py::arg("index"), py::arg("slice_bytes"), py::arg("stride"),
+        py::arg("m"));
+  // The FT_RTS_INDEXED payload around an opaque descriptor of
+  // _RTS_DESC_BYTES bytes; decode takes the message size the frame header
+  // announces and returns (index, slice_bytes, stride) or raises ValueError.
+  m.def("_index_desc_encode",
+        [](py::bytes desc, const std::vector<uint32_t>& index,
+           uint64_t slice_bytes, uint64_t stride) {
+          std::string d = desc;
+          if (d.size() != sizeof(RtsDesc))
+            throw py::value_error("index_desc_encode: descriptor must be "
+                                  "_RTS_DESC_BYTES long");
+          IndexRef ix;
+          ix.list = std::make_shared<const IndexList>(index);
+          ix.slice_bytes = slice_bytes;
+          ix.stride = stride;
+          std::vector<uint8_t> out = encode_rts_indexed(d.data(), d.size(), ix);
+          return py::bytes((const char*)out.data(), out.size());
+        },
+        py::arg("desc"), py::arg("index"), py::arg("slice_bytes"),
+        py::arg("stride"));
+  m.def("_index_desc_decode",
+        [](py::bytes payload, uint64_t size) {
+          std::string p = payload;
+          IndexRef ix;
+          std::string err;
+          if (!decode_rts_indexed((const uint8_t*)p.data(), p.size(),
+                                  sizeof(RtsDesc), size, &ix, &err))
+            throw py::value_error(err);
+          return py::make_tuple(*ix.list, ix.slice_bytes, ix.stride);
+        },
+        py::arg("payload"), py::arg("size"));
+  // One k_copy_indexed launch on raw device pointers; None for a dense
+  // side. The arguments are checked before any device is touched.
+  m.def("_copy_index_sync",
+        [](uintptr_t dst, py::object dst_index, uint64_t dst_slice,
+           uint64_t dst_stride, uintptr_t src, py::object src_index,
+           uint64_t src_slice, uint64_t src_stride, uint64_t bytes, int device,
+           size_t block_cap) {
+          if (dst_index.is_none() && src_index.is_none())
+            throw py::value_error("copy_index_sync: both sides are dense "
+                                  "(that is _copy_device_sync's)");
+          IndexRef di = hook_index_side(dst_index, dst_slice, dst_stride,
+                                        /*writable=*/true);
+          IndexRef si = hook_index_side(src_index, src_slice, src_stride,
+                                        /*writable=*/false);
+          if (di.on() && di.count() * dst_slice != bytes)
+            throw py::value_error(
+                "copy_index_sync: destination slices hold " +
+                std::to_string(di.count() * dst_slice) + " B, message " +
+                std::to_string(bytes));
+          if (si.on() && si.count() * src_slice != bytes)
+            throw py::value_error(
+                "copy_index_sync: source slices hold " +
+                std::to_string(si.count() * src_slice) + " B, message " +
+                std::to_string(bytes));
+          std::string err;
+          bool ok;
+          {
+            py::gil_scoped_release rel;
+            ok = gpu::copy_index_sync((void*)dst, di, (const void*)src, si,
+                                      bytes, device, block_cap, &err);
+          }
+          if (!ok) throw std::runtime_error("copy_index_sync: " + err);
+        },
+        py::arg("dst"), py::arg("dst_index"), py::arg("dst_slice"),
+        py::arg("dst_stride"), py::arg("src"), py::arg("src_index"),
+        py::arg("src_slice"), py::arg("src_stride"), py::arg("bytes"),
+        py::arg("device"), py::arg("block_cap") = 0);
   // Tile extents of k_copy_nd_tile: element bytes -> (T_A, T_B) elements.
   {
     py::dict tiles;

@@ -182,6 +182,45 @@ def _norm_buffer(buf: Any) -> Any:
     return buf
 
 
+class _IndexedShim:
+    """A torch HIP tensor used with ``index=``: its own shape and byte
+    strides, unmerged, so the core sees the first dimension it indexes."""
+
+    __slots__ = ("_t", "__cuda_array_interface__")
+
+    def __init__(self, t) -> None:
+        es = t.element_size()
+        self.__cuda_array_interface__ = {
+            "data": (t.data_ptr(), False),
+            "shape": tuple(t.shape),
+            "typestr": f"|V{es}",
+            "strides": tuple(s * es for s in t.stride()),
+            "version": 2,
+        }
+        self._t = t
+
+
+def _index_args(buffer: Any, index: Any, reduce: str | None = None):
+    """(buffer, keyword arguments) of a native send or recv with ``index=``.
+
+    ``index=idx`` makes the message the slices ``buffer[idx[0]],
+    buffer[idx[1]], ...`` in that order (a send), or writes message slice
+    ``r`` to ``buffer[idx[r]]`` (a receive). ``buffer`` is a device tensor
+    whose dimensions after the first are dense; ``idx`` is a host-side
+    sequence of ints, 1-D numpy integer array or 1-D CPU torch integer
+    tensor, validated and copied when the operation is posted. Every limit
+    is a ValueError whose text starts with ``index limit:``.
+    """
+    if index is None:
+        return _norm_buffer(buffer), {}
+    if reduce is not None:
+        raise ValueError("index limit: index= cannot be combined with "
+                         "reduce= (a reducing destination stays contiguous)")
+    if type(buffer).__module__.startswith("torch"):
+        buffer = _IndexedShim(buffer) if buffer.is_cuda else buffer.numpy()
+    return buffer, {"index": index}
+
+
 _REDUCE_OPS = ("sum",)
 _REDUCE_DTYPES = ("float32", "float16", "bfloat16", "int32")
 _TYPESTR_DTYPES = {"f4": "float32", "f2": "float16", "i4": "int32"}
@@ -255,17 +294,19 @@ class Server:
 
     # -- raw callback API ---------------------------------------------------
 
-    def send(self, client_ep, buffer, tag, done_callback, fail_callback):
+    def send(self, client_ep, buffer, tag, done_callback, fail_callback, *,
+             index=None):
+        buf, kw = _index_args(buffer, index)
         return self._server.send(
-            client_ep, _norm_buffer(buffer), tag, done_callback, fail_callback
+            client_ep, buf, tag, done_callback, fail_callback, **kw
         )
 
     def recv(self, buffer, tag, tag_mask, done_callback, fail_callback, *,
-             reduce: str | None = None):
-        kw = _reduce_args(buffer, reduce)
+             reduce: str | None = None, index=None):
+        buf, kw = _index_args(buffer, index, reduce)
+        kw.update(_reduce_args(buffer, reduce))
         return self._server.recv(
-            _norm_buffer(buffer), tag, tag_mask, done_callback, fail_callback,
-            **kw
+            buf, tag, tag_mask, done_callback, fail_callback, **kw
         )
 
     def flush(self, done_callback, fail_callback):
@@ -277,7 +318,10 @@ class Server:
     # -- asyncio API --------------------------------------------------------
 
     def asend(self, client_ep, buffer, tag: int,
-              loop: asyncio.AbstractEventLoop | None = None):
+              loop: asyncio.AbstractEventLoop | None = None, *, index=None):
+        """Post a send. ``index=idx`` sends the slices ``buffer[idx]`` of a
+        device tensor (see ``_index_args``)."""
+        buf, kw = _index_args(buffer, index)
         if loop is None:
             loop = asyncio.get_running_loop()
         ret: asyncio.Future[None] = asyncio.Future(loop=loop)
@@ -288,15 +332,18 @@ class Server:
         def bad(reason: str) -> None:
             _disp(ret.get_loop()).post(_set_exception, ret, reason)
 
-        self._server.send(client_ep, _norm_buffer(buffer), tag, ok, bad)
+        self._server.send(client_ep, buf, tag, ok, bad, **kw)
         return ret
 
     def arecv(self, buffer, tag: int, tag_mask: int,
               loop: asyncio.AbstractEventLoop | None = None, *,
-              reduce: str | None = None):
+              reduce: str | None = None, index=None):
         """Post a receive. ``reduce="sum"`` makes it a reducing receive
-        (see ``_reduce_args``): the message is added into the buffer."""
-        kw = _reduce_args(buffer, reduce)
+        (see ``_reduce_args``): the message is added into the buffer.
+        ``index=idx`` writes message slice ``r`` to ``buffer[idx[r]]`` (see
+        ``_index_args``)."""
+        buf, kw = _index_args(buffer, index, reduce)
+        kw.update(_reduce_args(buffer, reduce))
         if loop is None:
             loop = asyncio.get_running_loop()
         ret: asyncio.Future[tuple[int, int]] = asyncio.Future(loop=loop)
@@ -307,7 +354,7 @@ class Server:
         def bad(reason: str) -> None:
             _disp(ret.get_loop()).post(_set_exception, ret, reason)
 
-        self._server.recv(_norm_buffer(buffer), tag, tag_mask, ok, bad, **kw)
+        self._server.recv(buf, tag, tag_mask, ok, bad, **kw)
         return ret
 
     def aflush(self, loop: asyncio.AbstractEventLoop | None = None):
@@ -393,17 +440,16 @@ class Client:
 
     # -- raw callback API ---------------------------------------------------
 
-    def send(self, buffer, tag, done_callback, fail_callback):
-        return self._client.send(
-            _norm_buffer(buffer), tag, done_callback, fail_callback
-        )
+    def send(self, buffer, tag, done_callback, fail_callback, *, index=None):
+        buf, kw = _index_args(buffer, index)
+        return self._client.send(buf, tag, done_callback, fail_callback, **kw)
 
     def recv(self, buffer, tag, tag_mask, done_callback, fail_callback, *,
-             reduce: str | None = None):
-        kw = _reduce_args(buffer, reduce)
+             reduce: str | None = None, index=None):
+        buf, kw = _index_args(buffer, index, reduce)
+        kw.update(_reduce_args(buffer, reduce))
         return self._client.recv(
-            _norm_buffer(buffer), tag, tag_mask, done_callback, fail_callback,
-            **kw
+            buf, tag, tag_mask, done_callback, fail_callback, **kw
         )
 
     def flush(self, done_callback, fail_callback):
@@ -412,7 +458,10 @@ class Client:
     # -- asyncio API --------------------------------------------------------
 
     def asend(self, buffer, tag: int,
-              loop: asyncio.AbstractEventLoop | None = None):
+              loop: asyncio.AbstractEventLoop | None = None, *, index=None):
+        """Post a send. ``index=idx`` sends the slices ``buffer[idx]`` of a
+        device tensor (see ``_index_args``)."""
+        buf, kw = _index_args(buffer, index)
         if loop is None:
             loop = asyncio.get_running_loop()
         ret: asyncio.Future[None] = asyncio.Future(loop=loop)
@@ -423,15 +472,18 @@ class Client:
         def bad(reason: str) -> None:
             _disp(ret.get_loop()).post(_set_exception, ret, reason)
 
-        self._client.send(_norm_buffer(buffer), tag, ok, bad)
+        self._client.send(buf, tag, ok, bad, **kw)
         return ret
 
     def arecv(self, buffer, tag: int, tag_mask: int,
               loop: asyncio.AbstractEventLoop | None = None, *,
-              reduce: str | None = None):
+              reduce: str | None = None, index=None):
         """Post a receive. ``reduce="sum"`` makes it a reducing receive
-        (see ``_reduce_args``): the message is added into the buffer."""
-        kw = _reduce_args(buffer, reduce)
+        (see ``_reduce_args``): the message is added into the buffer.
+        ``index=idx`` writes message slice ``r`` to ``buffer[idx[r]]`` (see
+        ``_index_args``)."""
+        buf, kw = _index_args(buffer, index, reduce)
+        kw.update(_reduce_args(buffer, reduce))
         if loop is None:
             loop = asyncio.get_running_loop()
         ret: asyncio.Future[tuple[int, int]] = asyncio.Future(loop=loop)
@@ -442,7 +494,7 @@ class Client:
         def bad(reason: str) -> None:
             _disp(ret.get_loop()).post(_set_exception, ret, reason)
 
-        self._client.recv(_norm_buffer(buffer), tag, tag_mask, ok, bad, **kw)
+        self._client.recv(buf, tag, tag_mask, ok, bad, **kw)
         return ret
 
     def aflush(self, loop: asyncio.AbstractEventLoop | None = None):

@@ -38,7 +38,10 @@ class Server:
         tag: int,
         done_callback: Callable[[], None],
         fail_callback: Callable[[str], None],
-    ) -> None: ...
+        index: Index | None = None,
+    ) -> None:
+        """index=idx: the message is the slices buffer[idx[0]],
+        buffer[idx[1]], ... of a device tensor (see recv)."""
     def recv(
         self,
         buffer: Buffer,
@@ -48,11 +51,21 @@ class Server:
         fail_callback: Callable[[str], None],
         reduce: str = "",
         dtype: str = "",
+        index: Index | None = None,
     ) -> None:
         """reduce="sum" with dtype float32 / float16 / bfloat16 / int32: a
         reducing receive, buf[i] += msg[i] over length // itemsize elements.
         ValueError for an unknown op, a host buffer, another dtype, a
-        non-contiguous destination or one not aligned to its item size."""
+        non-contiguous destination or one not aligned to its item size.
+
+        index=idx: message slice r is written to buffer[idx[r]]. The buffer
+        is a device tensor exporting its own shape and byte strides, dense
+        after the first dimension; idx is a host-side sequence of ints, 1-D
+        numpy integer array or 1-D CPU torch integer tensor, validated and
+        copied here. ValueError starting "index limit:" for a host buffer,
+        a device / bool / float / non-1-D index, an entry out of range, a
+        repeated destination entry, more than _INDEX_MAX entries, non-dense
+        slices, overlapping destination slices, or index= with reduce=."""
     def flush(
         self, done_callback: Callable[[], None], fail_callback: Callable[[str], None]
     ) -> None: ...
@@ -82,7 +95,10 @@ class Client:
         tag: int,
         done_callback: Callable[[], None],
         fail_callback: Callable[[str], None],
-    ) -> None: ...
+        index: Index | None = None,
+    ) -> None:
+        """index=idx: the message is the slices buffer[idx[0]],
+        buffer[idx[1]], ... of a device tensor (see recv)."""
     def recv(
         self,
         buffer: Buffer,
@@ -92,11 +108,21 @@ class Client:
         fail_callback: Callable[[str], None],
         reduce: str = "",
         dtype: str = "",
+        index: Index | None = None,
     ) -> None:
         """reduce="sum" with dtype float32 / float16 / bfloat16 / int32: a
         reducing receive, buf[i] += msg[i] over length // itemsize elements.
         ValueError for an unknown op, a host buffer, another dtype, a
-        non-contiguous destination or one not aligned to its item size."""
+        non-contiguous destination or one not aligned to its item size.
+
+        index=idx: message slice r is written to buffer[idx[r]]. The buffer
+        is a device tensor exporting its own shape and byte strides, dense
+        after the first dimension; idx is a host-side sequence of ints, 1-D
+        numpy integer array or 1-D CPU torch integer tensor, validated and
+        copied here. ValueError starting "index limit:" for a host buffer,
+        a device / bool / float / non-1-D index, an entry out of range, a
+        repeated destination entry, more than _INDEX_MAX entries, non-dense
+        slices, overlapping destination slices, or index= with reduce=."""
     def flush(
         self, done_callback: Callable[[], None], fail_callback: Callable[[str], None]
     ) -> None: ...
@@ -167,6 +193,39 @@ def _copy_nd_sync(
 # k_copy_nd_tile tile extents: element bytes -> (T_A, T_B) in elements.
 _ND_TILE: dict[int, tuple[int, int]]
 _ND_MAX_DIMS: int
+
+# Indexed buffers (csrc/index.hpp). All but _copy_index_sync are host-only.
+Index = Any  # sequence of ints, 1-D numpy integer array, 1-D CPU torch tensor
+_INDEX_MAX: int  # kIndexMax: most entries one index list may hold
+_RTS_DESC_BYTES: int  # sizeof(RtsDesc)
+_PROTO_VERSION: int
+_FT_RTS_INDEXED: int
+
+def _plan_index(index: Index, extent: int, writable: bool = False) -> list[int]:
+    """The validated u32 list for a buffer of `extent` slices, or ValueError
+    ("index limit: ..."); writable=True also refuses a repeated entry."""
+
+def _index_offset(index: list[int], slice_bytes: int, stride: int, m: int) -> int:
+    """Byte offset from the buffer's base of message byte m:
+    index[m // slice_bytes] * stride + m % slice_bytes, in 64 bits."""
+
+def _index_desc_encode(
+    desc: bytes, index: list[int], slice_bytes: int, stride: int
+) -> bytes:
+    """The FT_RTS_INDEXED payload around a descriptor of _RTS_DESC_BYTES."""
+
+def _index_desc_decode(payload: bytes, size: int) -> tuple[list[int], int, int]:
+    """(index, slice_bytes, stride) of a payload announcing `size` message
+    bytes; ValueError for a malformed one."""
+
+def _copy_index_sync(
+    dst: int, dst_index: list[int] | None, dst_slice: int, dst_stride: int,
+    src: int, src_index: list[int] | None, src_slice: int, src_stride: int,
+    bytes: int, device: int, block_cap: int = 0,
+) -> None:
+    """One k_copy_indexed launch on raw device pointers, synchronous; None
+    for a dense side. ValueError, before any device is touched, for two
+    dense sides or slices that do not multiply out to `bytes`."""
 
 # Test hooks for the small-message kernels (csrc/smallmsg.hip). They call the
 # host functions the engine calls; every wait has a host deadline of ~2 s.
