@@ -19,8 +19,8 @@ PKG = REPO / "starway_amd"
 
 ENGINE_SOURCES = ["engine.cpp", "engine_wire.cpp", "engine_match.cpp",
                   "engine_planes.cpp"]
-SOURCES = [*ENGINE_SOURCES, "gpu.cpp", "module.cpp", "kernels.hip",
-           "smallmsg.hip"]
+SOURCES = [*ENGINE_SOURCES, "gpu.cpp", "module.cpp", "buffer_parse.cpp",
+           "module_hooks.cpp", "kernels.hip", "smallmsg.hip"]
 RCCL_SOURCES = ["rccl_group.cpp"]
 
 HIPCC = os.environ.get("STARWAY_HIPCC", "hipcc")

@@ -13,9 +13,9 @@ struct CopyTuning {
   size_t nt_threshold;  // bulk bytes at/above which the non-temporal kernels
                         // run (STARWAY_NT_THRESHOLD)
   int nt_unroll;        // >= 8 selects the x8 NT kernel (STARWAY_COPY_UNROLL)
-  // Tile-contiguous streaming kernel (copy_stream.hpp). Appended, so
-  // CopyTuning{block_cap, nt_threshold, nt_unroll} leaves both at 0, which
-  // the hooks resolve to the process default.
+  // Build one with designated initialisers (CopyTuning{.block_cap = n}): a
+  // field left out is 0, which the hooks resolve to the process default.
+  // Tile-contiguous streaming kernel (copy_stream.hpp).
   size_t stream_threshold = 0;  // bulk bytes at/above which it runs
                                 // (STARWAY_STREAM_THRESHOLD)
   size_t stream_blocks = 0;     // its grid cap (STARWAY_STREAM_BLOCKS)

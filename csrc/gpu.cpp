@@ -8,6 +8,7 @@
 //   * completion = hipEvent recorded on the pull stream, polled by the
 //     engine's progress loop (the ucp_worker_progress analog)
 #include "core.hpp"
+#include "gpu_hooks.hpp"
 #include "gpu_internal.hpp"
 #include "kernels.hpp"
 
@@ -1079,7 +1080,7 @@ bool copy_device_sync(void* dst, const void* src, size_t n, int device,
 bool copy_strided_sync(void* dst, uint64_t dst_stride, const void* src,
                        uint64_t src_stride, uint64_t rows, uint64_t row_bytes,
                        int device, size_t block_cap, std::string* err) {
-  CopyTuning t = resolve_tuning(CopyTuning{block_cap, 0, 0});
+  CopyTuning t = resolve_tuning(CopyTuning{.block_cap = block_cap});
   return run_sync(device, err, [&](hipStream_t stream) {
     return launch_copy_strided_tuned(dst, dst_stride, src, src_stride, rows,
                                      row_bytes, stream, t);
@@ -1090,7 +1091,7 @@ bool copy_nd_sync(void* dst, const Layout& dst_layout, const void* src,
                   const Layout& src_layout, uint64_t bytes, int device,
                   size_t block_cap, CopyNdPath path, bool* ineligible,
                   std::string* err) {
-  CopyTuning t = resolve_tuning(CopyTuning{block_cap, 0, 0});
+  CopyTuning t = resolve_tuning(CopyTuning{.block_cap = block_cap});
   *ineligible = path == CopyNdPath::Tiled &&
                 !copy_nd_tile_eligible(src_layout, dst_layout, src, dst);
   if (*ineligible) {
@@ -1110,7 +1111,7 @@ int copy_nd_tile_extent(int elem_bytes) {
 bool copy_index_sync(void* dst, const IndexRef& dst_index, const void* src,
                      const IndexRef& src_index, uint64_t bytes, int device,
                      size_t block_cap, std::string* err) {
-  CopyTuning t = resolve_tuning(CopyTuning{block_cap, 0, 0});
+  CopyTuning t = resolve_tuning(CopyTuning{.block_cap = block_cap});
   IndexUpload up;
   const bool ok = run_sync(device, err, [&](hipStream_t stream) {
     return copy_indexed(dst, dst_index, src, src_index, bytes, device, stream,

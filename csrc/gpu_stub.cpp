@@ -1,8 +1,9 @@
 // GPU-less stub of the gpu:: interface for sanitizer builds (TSAN/ASAN
-// stress binary, csrc/tsan_stress_main.cpp). The engine's cross-thread
+// stress binary, csrc/sanitizer_stress_main.cpp). The engine's cross-thread
 // contracts are identical with or without a device, so the host transport
 // paths (TCP, shm ring, CMA, tag matching, flush, teardown) run fully
-// instrumented without linking HIP.
+// instrumented without linking HIP. It holds exactly what the engine files
+// reference: the link of the stress binary is the check.
 #include "core.hpp"
 
 namespace sw {
@@ -10,8 +11,6 @@ namespace gpu {
 
 bool available() { return false; }
 int device_count() { return 0; }
-int current_device() { return -1; }
-int device_of(const void*) { return -1; }
 
 bool make_rts(const BufferRef&, RtsDesc*, std::string* err) {
   *err = "no GPU (sanitizer stub)";
@@ -37,48 +36,12 @@ void* begin_d2h(void*, const BufferRef&, std::string* err) {
 void attach_bounce(void*, RawBuf&&) {}
 int poll_ticket(void*, std::string*) { return -1; }
 void free_ticket(void*) {}
-void synchronize_all() {}
-CopyTuning copy_tuning() { return CopyTuning{8192, (size_t)64 << 20, 4}; }
-int copy_stream_unroll() { return 4; }
-bool copy_device_sync(void*, const void*, size_t, int, const CopyTuning&,
-                      std::string* err) {
-  *err = "no GPU (sanitizer stub)";
-  return false;
-}
-bool copy_strided_sync(void*, uint64_t, const void*, uint64_t, uint64_t,
-                       uint64_t, int, size_t, std::string* err) {
-  *err = "no GPU (sanitizer stub)";
-  return false;
-}
-bool copy_nd_sync(void*, const Layout&, const void*, const Layout&, uint64_t,
-                  int, size_t, CopyNdPath, bool* ineligible,
-                  std::string* err) {
-  *ineligible = false;
-  *err = "no GPU (sanitizer stub)";
-  return false;
-}
-int copy_nd_tile_extent(int) { return 0; }
-bool copy_index_sync(void*, const IndexRef&, const void*, const IndexRef&,
-                     uint64_t, int, size_t, std::string* err) {
-  *err = "no GPU (sanitizer stub)";
-  return false;
-}
-bool copy_multi_sync(const CopyDesc*, int, int, std::string* err) {
-  *err = "no GPU (sanitizer stub)";
-  return false;
-}
-bool accum_sync(void*, const void*, size_t, ElemType, int, const CopyTuning&,
-                std::string* err) {
-  *err = "no GPU (sanitizer stub)";
-  return false;
-}
 double same_gpu_copy_gbps() { return 3100.0; }
 double xgmi_link_gbps() { return 140.0; }
 bool calibrate(bool, std::string* err) {
   *err = "no GPU (sanitizer stub)";
   return false;
 }
-void ipc_close_all() {}
 
 bool inbox_create(InboxInfo*, int, std::string* err) {
   *err = "no GPU (sanitizer stub)";
@@ -108,40 +71,7 @@ void* arm_recv(const InboxInfo&, uint64_t, uint64_t, uint64_t, uint8_t*,
 int arm_poll(void*, uint64_t*) { return 4; }
 void arm_cancel(void*) {}
 void arm_free(void*) {}
-bool inbox_ring_read(const InboxInfo&, uint8_t*, std::string* err) {
-  *err = "no GPU (sanitizer stub)";
-  return false;
-}
-bool inbox_ring_write(const InboxInfo&, uint64_t, const uint8_t*, uint64_t,
-                      std::string* err) {
-  *err = "no GPU (sanitizer stub)";
-  return false;
-}
-bool inbox_push_sync(const InboxInfo&, const PushMsg*, int, int,
-                     std::string* err) {
-  *err = "no GPU (sanitizer stub)";
-  return false;
-}
-bool inbox_unpack_sync(const InboxInfo&, const UnpackMsg*, int, int*,
-                       std::vector<uint8_t>*, std::string* err) {
-  *err = "no GPU (sanitizer stub)";
-  return false;
-}
-void* arm_begin(const InboxInfo&, uint64_t, uint64_t, uint64_t, uint8_t*,
-                uint64_t, unsigned, bool, std::string* err) {
-  *err = "no GPU (sanitizer stub)";
-  return nullptr;
-}
-bool arm_end(void*, int*, uint64_t*, std::string* err) {
-  *err = "no GPU (sanitizer stub)";
-  return false;
-}
-
-}  // namespace gpu
-}  // namespace sw
-
-namespace sw {
-namespace gpu {
 void arm_leak(void*) {}
+
 }  // namespace gpu
 }  // namespace sw

@@ -34,6 +34,7 @@
 // subsystem replaces what UCX's eager-short protocol + cuda_copy transport
 // would have done, reference benchmark.md:63-89.)
 #include "core.hpp"
+#include "gpu_hooks.hpp"
 #include "gpu_internal.hpp"
 
 #include <hip/hip_runtime.h>

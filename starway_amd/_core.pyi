@@ -157,6 +157,19 @@ def _accum_sync(
     multiples of the item size."""
 
 def _copy_tuning() -> dict[str, int]: ...
+def _copy_stream_tuning() -> dict[str, int]:
+    """Streaming-kernel defaults (csrc/copy_stream.hpp): stream_threshold,
+    stream_blocks and unroll, the production kernel's elements per lane per
+    tile (a tile is 256 * unroll elements of 16 B). Host only."""
+
+def _copy_stream_plan(
+    n16: int, stream_blocks: int = 0, block: int | None = None
+) -> dict[str, int]:
+    """Tile plan of the production streaming kernel for n16 bulk elements
+    under a grid cap (0 = the process default): tile, full_tiles, ragged,
+    tiles, grid. With `block`, also that workgroup's first_tile, last_tile
+    and n_tiles (it takes every grid-th tile from first_tile). ValueError
+    when the cap resolves to 0. Host only."""
 
 # N-D layouts (csrc/layout.hpp). A plan is (unit, [(extent, stride_bytes),
 # ...]): `unit` bytes of dense innermost run, then the dimensions outside
