@@ -32,7 +32,7 @@ constexpr int kMultiMax = 8;
 // stream_threshold value that no message reaches: the streaming kernel off.
 constexpr size_t kStreamNever = ~(size_t)0;
 
-// Which kernel an N-D copy (launch_copy_nd_tuned) runs. Auto is what
+// Which kernel an N-D copy (launch_copy_nd) runs. Auto is what
 // production uses; the hooks force one so tests and benches reach both.
 enum class CopyNdPath : int { Auto = 0, Generic = 1, Tiled = 2 };
 

@@ -527,7 +527,7 @@ void* import_ipc(const uint8_t* handle, int open_device, std::string* err) {
     e = hipIpcOpenMemHandle(&base, h, hipIpcMemLazyEnablePeerAccess);
   }
   if (e != hipSuccess) {
-    *err = std::string("hipIpcOpenMemHandle: ") + hipGetErrorString(e);
+    *err = hip_error("hipIpcOpenMemHandle", e);
     return nullptr;
   }
   g_import_cache[ck] = base;
@@ -543,7 +543,7 @@ static Ticket* finish_ticket(int device, hipStream_t stream, void* staging,
                              std::string* err) {
   if (launched != hipSuccess) {
     abandon_route(staging, index, stream);
-    *err = std::string(launch_what) + hipGetErrorString(launched);
+    *err = hip_error(launch_what, launched);
     return nullptr;
   }
   Ticket* t = new Ticket();
@@ -553,7 +553,7 @@ static Ticket* finish_ticket(int device, hipStream_t stream, void* staging,
   if (e != hipSuccess) {
     abandon_route(staging, index, stream);
     delete t;
-    *err = std::string(event_what) + hipGetErrorString(e);
+    *err = hip_error(event_what, e);
     return nullptr;
   }
   t->dev_staging = staging;
@@ -697,7 +697,7 @@ static hipError_t copy_indexed(void* dst, const IndexRef& di, const void* src,
     if (e != hipSuccess) return e;
     s = IndexSide{(const uint32_t*)(base + nd), si.slice_bytes, si.stride};
   }
-  return launch_copy_indexed_tuned(dst, d, src, s, size, stream, tuning);
+  return launch_copy_indexed(dst, d, src, s, size, stream, tuning);
 }
 
 // Pack a device source of any geometry into fresh contiguous device staging
@@ -908,8 +908,8 @@ void* begin_pull(const RtsDesc& rts, const IndexRef& src_index,
       }
     }
   }
-  return finish_ticket(run_dev, stream, staging, &up, e, "pull launch: ",
-                       "event: ", err);
+  return finish_ticket(run_dev, stream, staging, &up, e, "pull launch",
+                       "event", err);
 }
 
 void* begin_pull_multi(const PullReq* reqs, int n, std::string* err) {
@@ -937,8 +937,8 @@ void* begin_pull_multi(const PullReq* reqs, int n, std::string* err) {
   DeviceGuard on(run_dev);
   hipStream_t stream = pull_stream(run_dev, 0);
   hipError_t e = launch_copy_multi(descs, n, stream);
-  return finish_ticket(run_dev, stream, nullptr, nullptr, e, "multi pull: ",
-                       "multi pull: ", err);
+  return finish_ticket(run_dev, stream, nullptr, nullptr, e, "multi pull",
+                       "multi pull", err);
 }
 
 void* begin_h2d(const BufferRef& dst, const void* src, uint64_t size,
@@ -984,8 +984,8 @@ void* begin_h2d(const BufferRef& dst, const void* src, uint64_t size,
   } else {
     e = hipMemcpyAsync(dst.ptr, src, size, hipMemcpyHostToDevice, stream);
   }
-  return finish_ticket(dst.device, stream, staging, &up, e, "h2d: ", "h2d: ",
-                       err);
+  return finish_ticket(dst.device, stream, staging, &up, e, "h2d",
+                       "h2d", err);
 }
 
 void* begin_d2h(void* host_dst, const BufferRef& src, std::string* err) {
@@ -999,8 +999,8 @@ void* begin_d2h(void* host_dst, const BufferRef& src, std::string* err) {
   void* staging = nullptr;
   IndexUpload up;
   hipError_t e = download(host_dst, src, src.device, stream, &staging, &up);
-  return finish_ticket(src.device, stream, staging, &up, e, "d2h: ", "d2h: ",
-                       err);
+  return finish_ticket(src.device, stream, staging, &up, e, "d2h",
+                       "d2h", err);
 }
 
 void attach_bounce(void* ticket, RawBuf&& bounce) {
@@ -1012,7 +1012,7 @@ int poll_ticket(void* ticket, std::string* err) {
   hipError_t e = hipEventQuery(t->ev);
   if (e == hipSuccess) return 1;
   if (e == hipErrorNotReady) return 0;
-  *err = std::string("copy failed: ") + hipGetErrorString(e);
+  *err = hip_error("copy failed", e);
   return -1;
 }
 
@@ -1082,7 +1082,7 @@ bool copy_strided_sync(void* dst, uint64_t dst_stride, const void* src,
                        int device, size_t block_cap, std::string* err) {
   CopyTuning t = resolve_tuning(CopyTuning{.block_cap = block_cap});
   return run_sync(device, err, [&](hipStream_t stream) {
-    return launch_copy_strided_tuned(dst, dst_stride, src, src_stride, rows,
+    return launch_copy_strided(dst, dst_stride, src, src_stride, rows,
                                      row_bytes, stream, t);
   });
 }
@@ -1099,7 +1099,7 @@ bool copy_nd_sync(void* dst, const Layout& dst_layout, const void* src,
     return false;
   }
   return run_sync(device, err, [&](hipStream_t stream) {
-    return launch_copy_nd_tuned(dst, dst_layout, src, src_layout, bytes,
+    return launch_copy_nd(dst, dst_layout, src, src_layout, bytes,
                                 stream, t, path);
   });
 }
@@ -1134,7 +1134,7 @@ bool accum_sync(void* dst, const void* src, size_t nbytes, ElemType dtype,
   }
   CopyTuning t = resolve_tuning(tuning);
   return run_sync(device, err, [&](hipStream_t stream) {
-    return launch_accum_tuned(dst, src, nbytes, dtype, stream, t);
+    return launch_accum(dst, src, nbytes, dtype, stream, t);
   });
 }
 

@@ -43,7 +43,7 @@ struct CopyDesc {
 };
 bool copy_multi_sync(const CopyDesc* descs, int n, int device,
                      std::string* err);
-// The accumulate kernels (launch_accum_tuned): dst[i] += src[i] over
+// The accumulate kernels (launch_accum): dst[i] += src[i] over
 // nbytes / elem_size(dtype) elements. Refuses pointers or a length that
 // are not multiples of the element size.
 bool accum_sync(void* dst, const void* src, size_t nbytes, ElemType dtype,

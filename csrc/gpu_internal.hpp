@@ -33,6 +33,11 @@ class DeviceGuard {
   hipError_t status_ = hipSuccess;
 };
 
+// "what: <HIP's text for e>", the form of every error string of the layer.
+inline std::string hip_error(const char* what, hipError_t e) {
+  return std::string(what) + ": " + hipGetErrorString(e);
+}
+
 // Map a peer's exported allocation on open_device (cached per device x
 // handle; gpu.cpp). Shared by the pull path and the inbox push path.
 void* import_ipc(const uint8_t* handle, int open_device, std::string* err);

@@ -27,140 +27,109 @@
 
 #include <cstdint>
 #include <cstdlib>
+#include <type_traits>
+#include <utility>
 
+#include "block_copy.hpp"
 #include "copy_stream.hpp"
 #include "kernels.hpp"
 
 namespace sw {
 
-// ---------------------------------------------------------------------------
-// 16B-vector bulk copy (both pointers 16B-aligned), grid-stride, x4 unroll.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_copy_b128(
-    const uint4* __restrict__ src, uint4* __restrict__ dst, size_t n16) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  // 4 independent elements in flight per thread per iteration.
-  while (i + 3 * stride < n16) {
-    uint4 a = src[i];
-    uint4 b = src[i + stride];
-    uint4 c = src[i + 2 * stride];
-    uint4 d = src[i + 3 * stride];
-    dst[i] = a;
-    dst[i + stride] = b;
-    dst[i + 2 * stride] = c;
-    dst[i + 3 * stride] = d;
-    i += 4 * stride;
-  }
-  for (; i < n16; i += stride) dst[i] = src[i];
-}
-
-// Non-temporal variant: bypass-cache hints on both sides. Used for messages
-// past the LLC-thrash threshold (they are touched exactly once). The builtin
-// wants a native vector type, not HIP_vector_type.
+// The builtin non-temporal accesses want a native vector type, not
+// HIP_vector_type.
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
 
-__global__ __launch_bounds__(256) void k_copy_b128_nt(
+// 16 B load and store, plain or non-temporal. Non-temporal is for data that
+// is touched exactly once (messages past the LLC-thrash threshold, a large
+// accumulate source) and would otherwise sweep the cache.
+template <bool NT>
+__device__ __forceinline__ u32x4 ld16(const u32x4* p) {
+  if constexpr (NT) return __builtin_nontemporal_load(p);
+  else return *p;
+}
+template <bool NT>
+__device__ __forceinline__ void st16(u32x4 v, u32x4* p) {
+  if constexpr (NT) __builtin_nontemporal_store(v, p);
+  else *p = v;
+}
+
+// The access type of a G-byte granule.
+template <int G> struct GranuleT;
+template <> struct GranuleT<16> { using type = uint4; };
+template <> struct GranuleT<8> { using type = uint2; };
+template <> struct GranuleT<4> { using type = uint32_t; };
+template <> struct GranuleT<2> { using type = uint16_t; };
+template <> struct GranuleT<1> { using type = uint8_t; };
+
+// ---------------------------------------------------------------------------
+// 16B-vector bulk copy (both pointers 16B-aligned), grid-stride, U
+// independent elements in flight per thread per iteration. Production runs
+// <4, false>, <4, true> (bypass-cache hints on both sides, from
+// nt_threshold) and <8, true> (nt_unroll >= 8).
+//
+// One iteration is a pack expansion, not a `#pragma unroll` loop: the loop
+// is unrolled late in the compiler and comes out with other address
+// arithmetic and, at U = 8, another interleaving of loads and stores than
+// the straight-line statements the measurements in docs/benchmark.md were
+// taken with. The pack is straight-line from the start.
+// ---------------------------------------------------------------------------
+template <bool NT, size_t... K>
+__device__ __forceinline__ void copy16_each(const u32x4* src, u32x4* dst,
+                                            size_t i, size_t stride,
+                                            std::index_sequence<K...>) {
+  u32x4 v[] = {ld16<NT>(&src[i + K * stride])...};
+  (st16<NT>(v[K], &dst[i + K * stride]), ...);
+}
+
+template <int U, bool NT>
+__global__ __launch_bounds__(256) void k_copy_b128(
     const u32x4* __restrict__ src, u32x4* __restrict__ dst, size_t n16) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
-  while (i + 3 * stride < n16) {
-    u32x4 a = __builtin_nontemporal_load(&src[i]);
-    u32x4 b = __builtin_nontemporal_load(&src[i + stride]);
-    u32x4 c = __builtin_nontemporal_load(&src[i + 2 * stride]);
-    u32x4 d = __builtin_nontemporal_load(&src[i + 3 * stride]);
-    __builtin_nontemporal_store(a, &dst[i]);
-    __builtin_nontemporal_store(b, &dst[i + stride]);
-    __builtin_nontemporal_store(c, &dst[i + 2 * stride]);
-    __builtin_nontemporal_store(d, &dst[i + 3 * stride]);
-    i += 4 * stride;
+  while (i + (U - 1) * stride < n16) {
+    copy16_each<NT>(src, dst, i, stride, std::make_index_sequence<U>{});
+    i += U * stride;
   }
   for (; i < n16; i += stride) {
-    u32x4 a = __builtin_nontemporal_load(&src[i]);
-    __builtin_nontemporal_store(a, &dst[i]);
+    u32x4 v = ld16<NT>(&src[i]);
+    st16<NT>(v, &dst[i]);
   }
 }
 
-// Deeper-unroll NT variant (8 independent 16B elements in flight/thread).
-__global__ __launch_bounds__(256) void k_copy_b128_nt_u8(
-    const u32x4* __restrict__ src, u32x4* __restrict__ dst, size_t n16) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  while (i + 7 * stride < n16) {
-    u32x4 v0 = __builtin_nontemporal_load(&src[i]);
-    u32x4 v1 = __builtin_nontemporal_load(&src[i + stride]);
-    u32x4 v2 = __builtin_nontemporal_load(&src[i + 2 * stride]);
-    u32x4 v3 = __builtin_nontemporal_load(&src[i + 3 * stride]);
-    u32x4 v4 = __builtin_nontemporal_load(&src[i + 4 * stride]);
-    u32x4 v5 = __builtin_nontemporal_load(&src[i + 5 * stride]);
-    u32x4 v6 = __builtin_nontemporal_load(&src[i + 6 * stride]);
-    u32x4 v7 = __builtin_nontemporal_load(&src[i + 7 * stride]);
-    __builtin_nontemporal_store(v0, &dst[i]);
-    __builtin_nontemporal_store(v1, &dst[i + stride]);
-    __builtin_nontemporal_store(v2, &dst[i + 2 * stride]);
-    __builtin_nontemporal_store(v3, &dst[i + 3 * stride]);
-    __builtin_nontemporal_store(v4, &dst[i + 4 * stride]);
-    __builtin_nontemporal_store(v5, &dst[i + 5 * stride]);
-    __builtin_nontemporal_store(v6, &dst[i + 6 * stride]);
-    __builtin_nontemporal_store(v7, &dst[i + 7 * stride]);
-    i += 8 * stride;
-  }
-  for (; i < n16; i += stride) {
-    u32x4 a = __builtin_nontemporal_load(&src[i]);
-    __builtin_nontemporal_store(a, &dst[i]);
-  }
-}
-
-// Byte-granularity fallback for arbitrary (mis)alignment.
-__global__ __launch_bounds__(256) void k_copy_b8(
-    const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, size_t n) {
+// Element-granularity fallback: G = 1 for arbitrary (mis)alignment, heads
+// and tails; G = 4 when both sides are 4B-co-aligned but not 16B.
+template <int G>
+__global__ __launch_bounds__(256) void k_copy_elem(
+    const typename GranuleT<G>::type* __restrict__ src,
+    typename GranuleT<G>::type* __restrict__ dst, size_t n) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (; i < n; i += stride) dst[i] = src[i];
 }
 
-// dword fallback when both sides are 4B-co-aligned but not 16B.
-__global__ __launch_bounds__(256) void k_copy_b32(
-    const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, size_t n4) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (; i < n4; i += stride) dst[i] = src[i];
-}
-
 // ---------------------------------------------------------------------------
 // Strided (2D) pack/unpack copy: row r of the message lives at
-// src + r*src_stride and lands at dst + r*dst_stride; rows are dense
-// row_bytes-long runs. Used for non-contiguous device tensors (e.g. torch
-// slices) so they move without a .contiguous() staging pass. Lanes walk
-// 16B elements in row-major message order, so global accesses stay
-// coalesced within each row.
+// src + r*src_stride and lands at dst + r*dst_stride; rows are dense runs of
+// row_n G-byte granules (G = 16 when everything is 16B-aligned, else 1).
+// Used for non-contiguous device tensors (e.g. torch slices) so they move
+// without a .contiguous() staging pass. Lanes walk granules in row-major
+// message order, so global accesses stay coalesced within each row.
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_copy_strided_b128(
+template <int G>
+__global__ __launch_bounds__(256) void k_copy_strided(
     const uint8_t* __restrict__ src, uint64_t src_stride,
     uint8_t* __restrict__ dst, uint64_t dst_stride, uint64_t rows,
-    uint64_t row_n16) {
+    uint64_t row_n) {
+  using V = typename GranuleT<G>::type;
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
-  const size_t total = (size_t)rows * row_n16;
+  const size_t total = (size_t)rows * row_n;
   for (; i < total; i += stride) {
-    size_t r = i / row_n16;
-    size_t c = i - r * row_n16;
-    *(uint4*)(dst + r * dst_stride + c * 16) =
-        *(const uint4*)(src + r * src_stride + c * 16);
-  }
-}
-
-__global__ __launch_bounds__(256) void k_copy_strided_b8(
-    const uint8_t* __restrict__ src, uint64_t src_stride,
-    uint8_t* __restrict__ dst, uint64_t dst_stride, uint64_t rows,
-    uint64_t row_bytes) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  const size_t total = (size_t)rows * row_bytes;
-  for (; i < total; i += stride) {
-    size_t r = i / row_bytes;
-    size_t c = i - r * row_bytes;
-    dst[r * dst_stride + c] = src[r * src_stride + c];
+    size_t r = i / row_n;
+    size_t c = i - r * row_n;
+    *(V*)(dst + r * dst_stride + c * G) =
+        *(const V*)(src + r * src_stride + c * G);
   }
 }
 
@@ -178,19 +147,9 @@ struct MultiCopyArgs {
 
 __global__ __launch_bounds__(256) void k_copy_multi(MultiCopyArgs args) {
   const MultiCopyDesc& m = args.d[blockIdx.x];
-  uintptr_t sp = (uintptr_t)m.src, dp = (uintptr_t)m.dst;
-  uint32_t bytes = m.bytes;
-  if ((sp & 15) == 0 && (dp & 15) == 0 && (bytes & 15) == 0) {
-    const uint4* s4 = (const uint4*)sp;
-    uint4* d4 = (uint4*)dp;
-    for (uint32_t i = threadIdx.x; i < bytes / 16; i += blockDim.x)
-      d4[i] = s4[i];
-  } else {
-    const uint8_t* s1 = (const uint8_t*)sp;
-    uint8_t* d1 = (uint8_t*)dp;
-    for (uint32_t i = threadIdx.x; i < bytes; i += blockDim.x)
-      d1[i] = s1[i];
-  }
+  block_copy(m.dst, m.src, m.bytes,
+             ((uintptr_t)m.src & 15) == 0 && ((uintptr_t)m.dst & 15) == 0 &&
+                 (m.bytes & 15) == 0);
 }
 
 hipError_t launch_copy_multi(const MultiCopyDesc* descs, int n,
@@ -224,29 +183,27 @@ constexpr size_t kStreamDefaultBlocks = 8192;
 // win for both types.
 constexpr size_t kAccumNtDefaultThreshold = (size_t)192 << 20;
 
+// Empty or unset gives the default, anything else is read as decimal.
+static size_t env_size(const char* name, size_t dflt) {
+  const char* v = getenv(name);
+  return v && *v ? (size_t)strtoull(v, nullptr, 10) : dflt;
+}
+
 const CopyTuning& default_copy_tuning() {
-  // Read once per process; STARWAY_COPY_BLOCKS / STARWAY_NT_THRESHOLD /
-  // STARWAY_COPY_UNROLL / STARWAY_STREAM_THRESHOLD / STARWAY_STREAM_BLOCKS
-  // exist for on-box sweeps (scripts/copy_tune.sh).
+  // Read once per process; the variables exist for on-box sweeps
+  // (scripts/copy_tune.sh).
   static const CopyTuning t = [] {
     CopyTuning d;
-    const char* v = getenv("STARWAY_COPY_BLOCKS");
-    d.block_cap = v && *v ? (size_t)strtoull(v, nullptr, 10) : (size_t)8192;
+    d.block_cap = env_size("STARWAY_COPY_BLOCKS", 8192);
     // NT past 64 MiB: the copy would otherwise sweep the 256 MiB LLC.
-    v = getenv("STARWAY_NT_THRESHOLD");
-    d.nt_threshold =
-        v && *v ? (size_t)strtoull(v, nullptr, 10) : (size_t)64 << 20;
-    v = getenv("STARWAY_COPY_UNROLL");
+    d.nt_threshold = env_size("STARWAY_NT_THRESHOLD", (size_t)64 << 20);
+    const char* v = getenv("STARWAY_COPY_UNROLL");
     d.nt_unroll = v && *v ? atoi(v) : 4;
-    v = getenv("STARWAY_STREAM_THRESHOLD");
-    d.stream_threshold = v && *v ? (size_t)strtoull(v, nullptr, 10)
-                                 : kStreamDefaultThreshold;
-    v = getenv("STARWAY_STREAM_BLOCKS");
-    d.stream_blocks = v && *v ? (size_t)strtoull(v, nullptr, 10)
-                              : kStreamDefaultBlocks;
-    v = getenv("STARWAY_ACCUM_NT_THRESHOLD");
-    d.accum_nt_threshold = v && *v ? (size_t)strtoull(v, nullptr, 10)
-                                   : kAccumNtDefaultThreshold;
+    d.stream_threshold =
+        env_size("STARWAY_STREAM_THRESHOLD", kStreamDefaultThreshold);
+    d.stream_blocks = env_size("STARWAY_STREAM_BLOCKS", kStreamDefaultBlocks);
+    d.accum_nt_threshold =
+        env_size("STARWAY_ACCUM_NT_THRESHOLD", kAccumNtDefaultThreshold);
     return d;
   }();
   return t;
@@ -260,6 +217,40 @@ static inline int copy_grid(size_t work_items, size_t cap) {
   return (int)blocks;
 }
 
+// A runtime granule (1/2/4/8/16 bytes; anything else counts as 1) as a
+// compile-time constant: f(std::integral_constant<int, G>{}).
+template <class F>
+static void with_granule(uint64_t g, F&& f) {
+  switch (g) {
+    case 16: f(std::integral_constant<int, 16>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    default: f(std::integral_constant<int, 1>{}); break;
+  }
+}
+
+// Index type of a kernel that divides by quantities the count `n` bounds:
+// f(uint32_t{}) where every value fits, else f(uint64_t{}). 64-bit division
+// costs several times the 32-bit one on gfx950.
+template <class F>
+static void with_index_width(uint64_t n, F&& f) {
+  if (n <= UINT32_MAX) f(uint32_t{});
+  else f(uint64_t{});
+}
+
+// The co-aligned split of a run of `bytes` at address p (the other side has
+// the same p & 15): `head` bytes up to the next 16B boundary, n16 whole 16 B
+// vectors, `tail` bytes.
+struct Split16 {
+  size_t head, n16, tail;
+};
+static inline Split16 split16(uintptr_t p, size_t bytes) {
+  size_t head = (16 - (p & 15)) & 15;
+  if (head > bytes) head = bytes;
+  return {head, (bytes - head) / 16, (bytes - head) & 15};
+}
+
 int copy_stream_unroll() { return kStreamProdU; }
 
 hipError_t launch_copy_tuned(void* dst, const void* src, size_t bytes,
@@ -268,54 +259,48 @@ hipError_t launch_copy_tuned(void* dst, const void* src, size_t bytes,
   const size_t cap = t.block_cap;
   uintptr_t s = (uintptr_t)src, d = (uintptr_t)dst;
   if ((s & 15) == (d & 15)) {
-    // Co-aligned: byte head to the next 16B boundary, vector bulk, byte tail.
-    size_t head = (16 - (s & 15)) & 15;
-    if (head > bytes) head = bytes;
-    if (head) {
-      hipLaunchKernelGGL(k_copy_b8, dim3(1), dim3(64), 0, stream,
-                         (const uint8_t*)src, (uint8_t*)dst, head);
-      s += head;
-      d += head;
-      bytes -= head;
-    }
-    size_t n16 = bytes / 16;
-    size_t tail = bytes & 15;
+    // Co-aligned: byte head, vector bulk, byte tail.
+    const auto [head, n16, tail] = split16(s, bytes);
+    if (head)
+      hipLaunchKernelGGL(k_copy_elem<1>, dim3(1), dim3(64), 0, stream,
+                         (const uint8_t*)s, (uint8_t*)d, head);
+    s += head;
+    d += head;
+    const u32x4* s16 = (const u32x4*)s;
+    u32x4* d16 = (u32x4*)d;
     if (n16) {
       if (n16 * 16 >= t.stream_threshold) {
         hipError_t e =
             launch_copy_stream<kStreamProdU, kStreamProdPolicy,
                                kStreamProdPrefetch>(
-                (void*)d, (const void*)s, n16,
-                t.stream_blocks ? t.stream_blocks : 1, stream);
+                d16, s16, n16, t.stream_blocks ? t.stream_blocks : 1, stream);
         if (e != hipSuccess) return e;
-      } else if (bytes >= t.nt_threshold) {
-        if (t.nt_unroll >= 8) {
-          hipLaunchKernelGGL(k_copy_b128_nt_u8,
+      } else if (bytes - head >= t.nt_threshold) {
+        if (t.nt_unroll >= 8)
+          hipLaunchKernelGGL((k_copy_b128<8, true>),
                              dim3(copy_grid(n16 / 8 + 1, cap)), dim3(256), 0,
-                             stream, (const u32x4*)s, (u32x4*)d, n16);
-        } else {
-          hipLaunchKernelGGL(k_copy_b128_nt,
+                             stream, s16, d16, n16);
+        else
+          hipLaunchKernelGGL((k_copy_b128<4, true>),
                              dim3(copy_grid(n16 / 4 + 1, cap)), dim3(256), 0,
-                             stream, (const u32x4*)s, (u32x4*)d, n16);
-        }
+                             stream, s16, d16, n16);
       } else {
-        hipLaunchKernelGGL(k_copy_b128, dim3(copy_grid(n16 / 4 + 1, cap)),
-                           dim3(256), 0, stream, (const uint4*)s, (uint4*)d,
-                           n16);
+        hipLaunchKernelGGL((k_copy_b128<4, false>),
+                           dim3(copy_grid(n16 / 4 + 1, cap)), dim3(256), 0,
+                           stream, s16, d16, n16);
       }
     }
-    if (tail) {
-      hipLaunchKernelGGL(k_copy_b8, dim3(1), dim3(64), 0, stream,
-                         (const uint8_t*)(s + n16 * 16),
-                         (uint8_t*)(d + n16 * 16), tail);
-    }
+    if (tail)
+      hipLaunchKernelGGL(k_copy_elem<1>, dim3(1), dim3(64), 0, stream,
+                         (const uint8_t*)(s16 + n16), (uint8_t*)(d16 + n16),
+                         tail);
   } else if ((s & 3) == (d & 3) && (s & 3) == 0 && (bytes & 3) == 0) {
     size_t n4 = bytes / 4;
-    hipLaunchKernelGGL(k_copy_b32, dim3(copy_grid(n4 / 4 + 1, cap)),
+    hipLaunchKernelGGL(k_copy_elem<4>, dim3(copy_grid(n4 / 4 + 1, cap)),
                        dim3(256), 0, stream, (const uint32_t*)src,
                        (uint32_t*)dst, n4);
   } else {
-    hipLaunchKernelGGL(k_copy_b8, dim3(copy_grid(bytes / 16 + 1, cap)),
+    hipLaunchKernelGGL(k_copy_elem<1>, dim3(copy_grid(bytes / 16 + 1, cap)),
                        dim3(256), 0, stream, (const uint8_t*)src,
                        (uint8_t*)dst, bytes);
   }
@@ -324,8 +309,7 @@ hipError_t launch_copy_tuned(void* dst, const void* src, size_t bytes,
 
 hipError_t launch_copy(void* dst, const void* src, size_t bytes,
                        hipStream_t stream, bool same_device) {
-  if (same_device)
-    return launch_copy_tuned(dst, src, bytes, stream, default_copy_tuning());
+  if (same_device) return launch_copy_tuned(dst, src, bytes, stream);
   // The streaming route was measured only for same-device copies; nothing
   // here can measure a pull over xGMI, and an unmeasured path does not
   // change: a cross-device pull keeps the grid-stride kernels.
@@ -334,11 +318,10 @@ hipError_t launch_copy(void* dst, const void* src, size_t bytes,
   return launch_copy_tuned(dst, src, bytes, stream, t);
 }
 
-hipError_t launch_copy_strided_tuned(void* dst, uint64_t dst_stride,
-                                     const void* src, uint64_t src_stride,
-                                     uint64_t rows, uint64_t row_bytes,
-                                     hipStream_t stream,
-                                     const CopyTuning& t) {
+hipError_t launch_copy_strided(void* dst, uint64_t dst_stride,
+                               const void* src, uint64_t src_stride,
+                               uint64_t rows, uint64_t row_bytes,
+                               hipStream_t stream, const CopyTuning& t) {
   if (rows == 0 || row_bytes == 0) return hipSuccess;
   const size_t cap = t.block_cap;
   uintptr_t s = (uintptr_t)src, d = (uintptr_t)dst;
@@ -347,13 +330,13 @@ hipError_t launch_copy_strided_tuned(void* dst, uint64_t dst_stride,
   if (vec) {
     uint64_t row_n16 = row_bytes / 16;
     size_t total = (size_t)rows * row_n16;
-    hipLaunchKernelGGL(k_copy_strided_b128,
+    hipLaunchKernelGGL(k_copy_strided<16>,
                        dim3(copy_grid(total / 4 + 1, cap)), dim3(256), 0,
                        stream, (const uint8_t*)src, src_stride, (uint8_t*)dst,
                        dst_stride, rows, row_n16);
   } else {
     size_t total = (size_t)rows * row_bytes;
-    hipLaunchKernelGGL(k_copy_strided_b8,
+    hipLaunchKernelGGL(k_copy_strided<1>,
                        dim3(copy_grid(total / 16 + 1, cap)), dim3(256), 0,
                        stream, (const uint8_t*)src, src_stride, (uint8_t*)dst,
                        dst_stride, rows, row_bytes);
@@ -361,26 +344,11 @@ hipError_t launch_copy_strided_tuned(void* dst, uint64_t dst_stride,
   return hipGetLastError();
 }
 
-hipError_t launch_copy_strided(void* dst, uint64_t dst_stride,
-                               const void* src, uint64_t src_stride,
-                               uint64_t rows, uint64_t row_bytes,
-                               hipStream_t stream) {
-  return launch_copy_strided_tuned(dst, dst_stride, src, src_stride, rows,
-                                   row_bytes, stream, default_copy_tuning());
-}
-
 // ---------------------------------------------------------------------------
 // N-D pack/unpack copy (layout.hpp): any strided view on either side, e.g.
 // a transposed matrix or a (B,H,S,D)->(B,S,H,D) permute. Serves only the
 // layouts the 2-D kernels above cannot express.
 // ---------------------------------------------------------------------------
-
-template <int G> struct GranuleT;
-template <> struct GranuleT<16> { using type = uint4; };
-template <> struct GranuleT<8> { using type = uint2; };
-template <> struct GranuleT<4> { using type = uint32_t; };
-template <> struct GranuleT<2> { using type = uint16_t; };
-template <> struct GranuleT<1> { using type = uint8_t; };
 
 // Byte offset of granule `i` (G = 1 << shift bytes each, message order)
 // from the view's base. G divides unit and every stride, so a granule never
@@ -559,31 +527,6 @@ bool copy_nd_tile_eligible(const Layout& sl, const Layout& dl, const void* src,
   return tile_plan(sl, dl, src, dst, &s_is_src, &axis);
 }
 
-template <int E>
-static void launch_tile(const uint8_t* src, uint8_t* dst, const TileArgs& a,
-                        size_t cap, hipStream_t stream) {
-  size_t blocks = a.tiles < cap ? (size_t)a.tiles : cap;
-  hipLaunchKernelGGL(k_copy_nd_tile<E>, dim3((unsigned)blocks), dim3(256), 0,
-                     stream, src, dst, a);
-}
-
-template <int G>
-static void launch_nd(const uint8_t* src, const Layout& sl, uint8_t* dst,
-                      const Layout& dl, uint64_t bytes, size_t cap,
-                      hipStream_t stream) {
-  const uint64_t n = bytes / G;
-  const dim3 grid(copy_grid(n / 4 + 1, cap));
-  // 32-bit index arithmetic only where every value fits: the granule
-  // count bounds each quotient and (the message being non-empty) each
-  // extent.
-  if (n <= UINT32_MAX)
-    hipLaunchKernelGGL((k_copy_nd<G, uint32_t>), grid, dim3(256), 0, stream,
-                       src, sl, dst, dl, n);
-  else
-    hipLaunchKernelGGL((k_copy_nd<G, uint64_t>), grid, dim3(256), 0, stream,
-                       src, sl, dst, dl, n);
-}
-
 // Dispatch rule for CopyNdPath::Auto: the tiled kernel whenever the pair is
 // in the transpose family (tile_plan), i.e. the strided side's dense run is
 // a single element (<= 16 B), and dimension A fills at least half a tile
@@ -603,16 +546,18 @@ static void launch_nd(const uint8_t* src, const Layout& sl, uint8_t* dst,
 // half-row floor is reasoning, not measurement: with fewer elements along A
 // most lanes of the phase that runs along A idle, while the generic
 // kernel's message-order walk keeps the contiguous side coalesced.
-hipError_t launch_copy_nd_tuned(void* dst, const Layout& dl, const void* src,
-                                const Layout& sl, uint64_t bytes,
-                                hipStream_t stream, const CopyTuning& t,
-                                CopyNdPath path) {
+hipError_t launch_copy_nd(void* dst, const Layout& dl, const void* src,
+                          const Layout& sl, uint64_t bytes,
+                          hipStream_t stream, const CopyTuning& t,
+                          CopyNdPath path) {
   if (bytes == 0) return hipSuccess;
   bool s_is_src = false;
   int axis = -1;
   const bool eligible = tile_plan(sl, dl, src, dst, &s_is_src, &axis);
   if (path == CopyNdPath::Tiled && !eligible) return hipErrorInvalidValue;
   const size_t cap = t.block_cap;
+  const uint8_t* sp = (const uint8_t*)src;
+  uint8_t* dp = (uint8_t*)dst;
   if (eligible && path != CopyNdPath::Generic) {
     const Layout& s = s_is_src ? sl : dl;
     const int E = (int)s.unit;
@@ -645,36 +590,30 @@ hipError_t launch_copy_nd_tuned(void* dst, const Layout& dl, const void* src,
       a.tilesA = (a.nA + T - 1) / T;
       a.tilesB = (a.nB + T - 1) / T;
       a.tiles = a.tilesA * a.tilesB * batch;
-      const uint8_t* sp = (const uint8_t*)src;
-      uint8_t* dp = (uint8_t*)dst;
-      switch (E) {
-        case 1: launch_tile<1>(sp, dp, a, cap, stream); break;
-        case 2: launch_tile<2>(sp, dp, a, cap, stream); break;
-        case 4: launch_tile<4>(sp, dp, a, cap, stream); break;
-        case 8: launch_tile<8>(sp, dp, a, cap, stream); break;
-        default: launch_tile<16>(sp, dp, a, cap, stream); break;
-      }
+      const unsigned blocks =
+          (unsigned)(a.tiles < cap ? (size_t)a.tiles : cap);
+      // tile_plan admits single elements of 1/2/4/8/16 bytes only.
+      with_granule((uint64_t)E, [&](auto e) {
+        hipLaunchKernelGGL(k_copy_nd_tile<e()>, dim3(blocks), dim3(256), 0,
+                           stream, sp, dp, a);
+      });
       return hipGetLastError();
     }
   }
-  const uint8_t* sp = (const uint8_t*)src;
-  uint8_t* dp = (uint8_t*)dst;
-  switch (granule(sl, dl, (uint64_t)(uintptr_t)src,
-                  (uint64_t)(uintptr_t)dst)) {
-    case 16: launch_nd<16>(sp, sl, dp, dl, bytes, cap, stream); break;
-    case 8: launch_nd<8>(sp, sl, dp, dl, bytes, cap, stream); break;
-    case 4: launch_nd<4>(sp, sl, dp, dl, bytes, cap, stream); break;
-    case 2: launch_nd<2>(sp, sl, dp, dl, bytes, cap, stream); break;
-    default: launch_nd<1>(sp, sl, dp, dl, bytes, cap, stream); break;
-  }
+  with_granule(
+      granule(sl, dl, (uint64_t)(uintptr_t)src, (uint64_t)(uintptr_t)dst),
+      [&](auto g) {
+        const uint64_t n = bytes / g();
+        const dim3 grid(copy_grid(n / 4 + 1, cap));
+        // 32-bit index arithmetic only where every value fits: the granule
+        // count bounds each quotient and (the message being non-empty) each
+        // extent.
+        with_index_width(n, [&](auto idx) {
+          hipLaunchKernelGGL((k_copy_nd<g(), decltype(idx)>), grid, dim3(256),
+                             0, stream, sp, sl, dp, dl, n);
+        });
+      });
   return hipGetLastError();
-}
-
-hipError_t launch_copy_nd(void* dst, const Layout& dl, const void* src,
-                          const Layout& sl, uint64_t bytes,
-                          hipStream_t stream) {
-  return launch_copy_nd_tuned(dst, dl, src, sl, bytes, stream,
-                              default_copy_tuning(), CopyNdPath::Auto);
 }
 
 // ---------------------------------------------------------------------------
@@ -682,7 +621,7 @@ hipError_t launch_copy_nd(void* dst, const Layout& dl, const void* src,
 // either side or both, e.g. the scattered blocks of a paged KV cache. A side
 // with a null list is one dense run.
 //
-// The shape of k_copy_strided_b128 with a table lookup in place of the row
+// The shape of k_copy_strided<16> with a table lookup in place of the row
 // multiply: grid-stride over the message in G-byte granules, in message
 // order, so consecutive lanes take consecutive granules and accesses inside
 // a slice stay coalesced; x4 unroll, no LDS (nothing is reused). Per side
@@ -734,24 +673,10 @@ __global__ __launch_bounds__(256) void k_copy_indexed(
         *(const V*)(src + indexed_offset<Idx>(ss, (Idx)i, sg, shift));
 }
 
-template <int G>
-static void launch_indexed(const uint8_t* src, const IndexSide& ss,
-                           uint8_t* dst, const IndexSide& ds, uint64_t bytes,
-                           size_t cap, hipStream_t stream) {
-  const uint64_t n = bytes / G;
-  const dim3 grid(copy_grid(n / 4 + 1, cap));
-  if (n <= UINT32_MAX)
-    hipLaunchKernelGGL((k_copy_indexed<G, uint32_t>), grid, dim3(256), 0,
-                       stream, src, ss, dst, ds, n);
-  else
-    hipLaunchKernelGGL((k_copy_indexed<G, uint64_t>), grid, dim3(256), 0,
-                       stream, src, ss, dst, ds, n);
-}
-
-hipError_t launch_copy_indexed_tuned(void* dst, const IndexSide& ds,
-                                     const void* src, const IndexSide& ss,
-                                     uint64_t bytes, hipStream_t stream,
-                                     const CopyTuning& t) {
+hipError_t launch_copy_indexed(void* dst, const IndexSide& ds,
+                               const void* src, const IndexSide& ss,
+                               uint64_t bytes, hipStream_t stream,
+                               const CopyTuning& t) {
   if (bytes == 0) return hipSuccess;
   // Two dense sides are launch_copy's; an indexed side has whole, non-empty
   // slices that add up to the message.
@@ -762,22 +687,18 @@ hipError_t launch_copy_indexed_tuned(void* dst, const IndexSide& ds,
   const size_t cap = t.block_cap;
   const uint8_t* sp = (const uint8_t*)src;
   uint8_t* dp = (uint8_t*)dst;
-  switch (index_granule((uint64_t)(uintptr_t)dst, ds,
-                        (uint64_t)(uintptr_t)src, ss)) {
-    case 16: launch_indexed<16>(sp, ss, dp, ds, bytes, cap, stream); break;
-    case 8: launch_indexed<8>(sp, ss, dp, ds, bytes, cap, stream); break;
-    case 4: launch_indexed<4>(sp, ss, dp, ds, bytes, cap, stream); break;
-    case 2: launch_indexed<2>(sp, ss, dp, ds, bytes, cap, stream); break;
-    default: launch_indexed<1>(sp, ss, dp, ds, bytes, cap, stream); break;
-  }
+  with_granule(
+      index_granule((uint64_t)(uintptr_t)dst, ds, (uint64_t)(uintptr_t)src,
+                    ss),
+      [&](auto g) {
+        const uint64_t n = bytes / g();
+        const dim3 grid(copy_grid(n / 4 + 1, cap));
+        with_index_width(n, [&](auto idx) {
+          hipLaunchKernelGGL((k_copy_indexed<g(), decltype(idx)>), grid,
+                             dim3(256), 0, stream, sp, ss, dp, ds, n);
+        });
+      });
   return hipGetLastError();
-}
-
-hipError_t launch_copy_indexed(void* dst, const IndexSide& ds, const void* src,
-                               const IndexSide& ss, uint64_t bytes,
-                               hipStream_t stream) {
-  return launch_copy_indexed_tuned(dst, ds, src, ss, bytes, stream,
-                                   default_copy_tuning());
 }
 
 // ---------------------------------------------------------------------------
@@ -858,17 +779,10 @@ __device__ __forceinline__ u32x4 accum16(u32x4 d, u32x4 s) {
   return r;
 }
 
-// Source load of the bulk kernel: plain, or non-temporal for a large
-// source, which is read exactly once and would otherwise sweep the cache
-// the accumulator's read-modify-write lives in.
-template <bool NT>
-__device__ __forceinline__ u32x4 accum_src(const u32x4* p) {
-  if constexpr (NT) return __builtin_nontemporal_load(p);
-  else return *p;
-}
-
-// 16B-vector bulk accumulate (both pointers 16B-aligned). The destination
-// is read-modify-write and stays plain.
+// 16B-vector bulk accumulate (both pointers 16B-aligned). The source load
+// is plain, or non-temporal (NT) for a large source, which is read exactly
+// once and would otherwise sweep the cache the accumulator's
+// read-modify-write lives in. The destination stays plain.
 template <class A, bool NT>
 __global__ __launch_bounds__(256) void k_accum_b128(
     const u32x4* __restrict__ src, u32x4* __restrict__ dst, size_t n16) {
@@ -876,10 +790,10 @@ __global__ __launch_bounds__(256) void k_accum_b128(
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   // 4 + 4 independent loads in flight per thread per iteration.
   while (i + 3 * stride < n16) {
-    u32x4 s0 = accum_src<NT>(&src[i]);
-    u32x4 s1 = accum_src<NT>(&src[i + stride]);
-    u32x4 s2 = accum_src<NT>(&src[i + 2 * stride]);
-    u32x4 s3 = accum_src<NT>(&src[i + 3 * stride]);
+    u32x4 s0 = ld16<NT>(&src[i]);
+    u32x4 s1 = ld16<NT>(&src[i + stride]);
+    u32x4 s2 = ld16<NT>(&src[i + 2 * stride]);
+    u32x4 s3 = ld16<NT>(&src[i + 3 * stride]);
     u32x4 d0 = dst[i];
     u32x4 d1 = dst[i + stride];
     u32x4 d2 = dst[i + 2 * stride];
@@ -891,7 +805,7 @@ __global__ __launch_bounds__(256) void k_accum_b128(
     i += 4 * stride;
   }
   for (; i < n16; i += stride)
-    dst[i] = accum16<A>(dst[i], accum_src<NT>(&src[i]));
+    dst[i] = accum16<A>(dst[i], ld16<NT>(&src[i]));
 }
 
 // Element-granularity accumulate: heads, tails and pairs that are not 16B
@@ -912,26 +826,20 @@ static hipError_t launch_accum_t(void* dst, const void* src, size_t bytes,
   const size_t cap = t.block_cap;
   uintptr_t s = (uintptr_t)src, d = (uintptr_t)dst;
   if ((s & 15) == (d & 15)) {
-    // Co-aligned: element head to the next 16B boundary, vector bulk,
-    // element tail. 16 is a multiple of the element size, so head and tail
-    // are whole elements.
-    size_t head = (16 - (s & 15)) & 15;
-    if (head > bytes) head = bytes;
-    if (head) {
+    // Co-aligned: element head, vector bulk, element tail. 16 is a multiple
+    // of the element size, so head and tail are whole elements.
+    const auto [head, n16, tail] = split16(s, bytes);
+    if (head)
       hipLaunchKernelGGL(k_accum_elem<A>, dim3(1), dim3(64), 0, stream,
                          (const W*)s, (W*)d, head / sizeof(W));
-      s += head;
-      d += head;
-      bytes -= head;
-    }
-    const size_t n16 = bytes / 16;
-    const size_t tail = bytes & 15;
+    s += head;
+    d += head;
     if (n16) {
       const dim3 grid(copy_grid(n16 / 4 + 1, cap));
       // Non-temporal source loads from accum_nt_threshold, a knob of the
       // accumulate family's own: its crossover lies far above the copy
       // family's nt_threshold (see kAccumNtDefaultThreshold).
-      if (bytes >= t.accum_nt_threshold)
+      if (bytes - head >= t.accum_nt_threshold)
         hipLaunchKernelGGL((k_accum_b128<A, true>), grid, dim3(256), 0,
                            stream, (const u32x4*)s, (u32x4*)d, n16);
       else
@@ -952,9 +860,9 @@ static hipError_t launch_accum_t(void* dst, const void* src, size_t bytes,
 
 // dst and src must be aligned to the element size and `bytes` a multiple
 // of it (the callers in gpu.cpp guarantee both); src must not overlap dst.
-hipError_t launch_accum_tuned(void* dst, const void* src, size_t bytes,
-                              ElemType dtype, hipStream_t stream,
-                              const CopyTuning& t) {
+hipError_t launch_accum(void* dst, const void* src, size_t bytes,
+                        ElemType dtype, hipStream_t stream,
+                        const CopyTuning& t) {
   const size_t es = elem_size(dtype);
   if (es == 0 || bytes % es || ((uintptr_t)dst | (uintptr_t)src) % es)
     return hipErrorInvalidValue;
@@ -968,12 +876,6 @@ hipError_t launch_accum_tuned(void* dst, const void* src, size_t bytes,
     case ElemType::None: break;
   }
   return hipErrorInvalidValue;
-}
-
-hipError_t launch_accum(void* dst, const void* src, size_t bytes,
-                        ElemType dtype, hipStream_t stream) {
-  return launch_accum_tuned(dst, src, bytes, dtype, stream,
-                            default_copy_tuning());
 }
 
 }  // namespace sw

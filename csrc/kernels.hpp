@@ -30,28 +30,25 @@ hipError_t launch_copy_multi(const MultiCopyDesc* descs, int n,
 // may the copy take the streaming route (see launch_copy in kernels.hip).
 hipError_t launch_copy(void* dst, const void* src, size_t bytes,
                        hipStream_t stream, bool same_device);
+// The flat dispatch itself, under any tuning (hooks, bin/copy_bench).
 hipError_t launch_copy_tuned(void* dst, const void* src, size_t bytes,
-                             hipStream_t stream, const CopyTuning& t);
+                             hipStream_t stream,
+                             const CopyTuning& t = default_copy_tuning());
 // Elements per lane per tile (U) of the production streaming kernel.
 int copy_stream_unroll();
 
 hipError_t launch_copy_strided(void* dst, uint64_t dst_stride,
                                const void* src, uint64_t src_stride,
                                uint64_t rows, uint64_t row_bytes,
-                               hipStream_t stream);
-hipError_t launch_copy_strided_tuned(void* dst, uint64_t dst_stride,
-                                     const void* src, uint64_t src_stride,
-                                     uint64_t rows, uint64_t row_bytes,
-                                     hipStream_t stream, const CopyTuning& t);
+                               hipStream_t stream,
+                               const CopyTuning& t = default_copy_tuning());
 
 // Both layouts describe `bytes` message bytes.
 hipError_t launch_copy_nd(void* dst, const Layout& dst_layout,
                           const void* src, const Layout& src_layout,
-                          uint64_t bytes, hipStream_t stream);
-hipError_t launch_copy_nd_tuned(void* dst, const Layout& dst_layout,
-                                const void* src, const Layout& src_layout,
-                                uint64_t bytes, hipStream_t stream,
-                                const CopyTuning& t, CopyNdPath path);
+                          uint64_t bytes, hipStream_t stream,
+                          const CopyTuning& t = default_copy_tuning(),
+                          CopyNdPath path = CopyNdPath::Auto);
 // Tile extent (elements, both axes) of k_copy_nd_tile per element size; 0
 // for an unsupported size.
 int copy_nd_tile_extent(int elem_bytes);
@@ -65,18 +62,13 @@ bool copy_nd_tile_eligible(const Layout& src_layout, const Layout& dst_layout,
 // least one side is indexed; each indexed side's slices add up to `bytes`.
 hipError_t launch_copy_indexed(void* dst, const IndexSide& dst_side,
                                const void* src, const IndexSide& src_side,
-                               uint64_t bytes, hipStream_t stream);
-hipError_t launch_copy_indexed_tuned(void* dst, const IndexSide& dst_side,
-                                     const void* src,
-                                     const IndexSide& src_side, uint64_t bytes,
-                                     hipStream_t stream, const CopyTuning& t);
+                               uint64_t bytes, hipStream_t stream,
+                               const CopyTuning& t = default_copy_tuning());
 
 // dst[i] += src[i]; both pointers aligned to the element size, bytes a
 // multiple of it, no overlap.
 hipError_t launch_accum(void* dst, const void* src, size_t bytes,
-                        ElemType dtype, hipStream_t stream);
-hipError_t launch_accum_tuned(void* dst, const void* src, size_t bytes,
-                              ElemType dtype, hipStream_t stream,
-                              const CopyTuning& t);
+                        ElemType dtype, hipStream_t stream,
+                        const CopyTuning& t = default_copy_tuning());
 
 }  // namespace sw

@@ -33,6 +33,7 @@
 // (Reference parity note: the reference had no GPU path at all — this
 // subsystem replaces what UCX's eager-short protocol + cuda_copy transport
 // would have done, reference benchmark.md:63-89.)
+#include "block_copy.hpp"
 #include "core.hpp"
 #include "gpu_hooks.hpp"
 #include "gpu_internal.hpp"
@@ -81,16 +82,9 @@ __global__ __launch_bounds__(256) void k_inbox_push(PushArgs args) {
     *(unsigned long long*)(m.slot + 8) = m.tag;
     *(unsigned long long*)(m.slot + 16) = (unsigned long long)m.size;
   }
-  uintptr_t sp = (uintptr_t)m.src;
-  if ((sp & 15) == 0 && (m.size & 15) == 0) {
-    const uint4* s4 = (const uint4*)sp;
-    uint4* d4 = (uint4*)payload;
-    for (uint32_t i = threadIdx.x; i < m.size / 16; i += blockDim.x)
-      d4[i] = s4[i];
-  } else {
-    for (uint32_t i = threadIdx.x; i < m.size; i += blockDim.x)
-      payload[i] = m.src[i];
-  }
+  // Slot payloads are 64 B-aligned: only the source decides.
+  block_copy(payload, m.src, m.size,
+             ((uintptr_t)m.src & 15) == 0 && (m.size & 15) == 0);
   // Publish: every storing wave drains, one lane releases the seq word.
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -134,17 +128,8 @@ __global__ __launch_bounds__(256) void k_inbox_unpack(UnpackArgs args) {
   }
   __syncthreads();
   if (ok) {
-    const uint8_t* payload = m.slot + kInboxHdrBytes;
-    uintptr_t dp = (uintptr_t)m.dst;
-    if ((dp & 15) == 0 && (m.size & 15) == 0) {
-      const uint4* s4 = (const uint4*)payload;
-      uint4* d4 = (uint4*)dp;
-      for (uint32_t i = threadIdx.x; i < m.size / 16; i += blockDim.x)
-        d4[i] = s4[i];
-    } else {
-      for (uint32_t i = threadIdx.x; i < m.size; i += blockDim.x)
-        m.dst[i] = payload[i];
-    }
+    block_copy(m.dst, m.slot + kInboxHdrBytes, m.size,
+               ((uintptr_t)m.dst & 15) == 0 && (m.size & 15) == 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
   __syncthreads();
@@ -213,17 +198,8 @@ __global__ __launch_bounds__(256) void k_inbox_wait(ArmArgs a) {
   unsigned long long status = st;
   if ((status & 0xFF) == 1) {
     uint32_t size = (uint32_t)(status >> 32);
-    const uint8_t* payload = a.slot + kInboxHdrBytes;
-    uintptr_t dp = (uintptr_t)a.dst;
-    if ((dp & 15) == 0 && (size & 15) == 0) {
-      const uint4* s4 = (const uint4*)payload;
-      uint4* d4 = (uint4*)dp;
-      for (uint32_t i = threadIdx.x; i < size / 16; i += blockDim.x)
-        d4[i] = s4[i];
-    } else {
-      for (uint32_t i = threadIdx.x; i < size; i += blockDim.x)
-        a.dst[i] = payload[i];
-    }
+    block_copy(a.dst, a.slot + kInboxHdrBytes, size,
+               ((uintptr_t)a.dst & 15) == 0 && (size & 15) == 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
   __syncthreads();
@@ -346,7 +322,7 @@ bool inbox_create(InboxInfo* out, int device, std::string* err) {
     }
     hipError_t e = hipMalloc(&base, (size_t)slots * slot_bytes);
     if (e != hipSuccess) {
-      *err = std::string("inbox alloc: ") + hipGetErrorString(e);
+      *err = hip_error("inbox alloc", e);
       return false;
     }
     hipMemset(base, 0, (size_t)slots * slot_bytes);
@@ -354,7 +330,7 @@ bool inbox_create(InboxInfo* out, int device, std::string* err) {
     e = hipIpcGetMemHandle(&h, base);
     if (e != hipSuccess) {
       hipFree(base);
-      *err = std::string("inbox export: ") + hipGetErrorString(e);
+      *err = hip_error("inbox export", e);
       return false;
     }
   }
@@ -401,6 +377,11 @@ void inbox_destroy(const InboxInfo& ib) {
   hipFree((void*)(uintptr_t)ib.base);
 }
 
+// The slot that sequence number `seq` lands in, in a ring mapped at `base`.
+static uint8_t* slot_of(const InboxInfo& ring, uint8_t* base, uint64_t seq) {
+  return base + (seq % ring.slots) * ring.slot_bytes;
+}
+
 // Resolve the peer's inbox base in OUR address space: raw pointer when the
 // peer is this very process (loopback), else the cached hipIpc mapping.
 static uint8_t* peer_inbox_base(const InboxInfo& peer, bool same_proc,
@@ -431,7 +412,7 @@ void* inbox_push(const InboxInfo& peer, bool same_proc, int run_device,
   args.n = n;
   for (int i = 0; i < n; i++) {
     args.d[i].src = msgs[i].src;
-    args.d[i].slot = base + (msgs[i].seq % peer.slots) * peer.slot_bytes;
+    args.d[i].slot = slot_of(peer, base, msgs[i].seq);
     args.d[i].size = msgs[i].size;
     args.d[i].seq = msgs[i].seq;
     args.d[i].tag = msgs[i].tag;
@@ -448,7 +429,7 @@ void* inbox_push(const InboxInfo& peer, bool same_proc, int run_device,
     if (e == hipSuccess) e = hipEventRecord(t->ev, stream);
   }
   if (e != hipSuccess) {
-    *err = std::string("inbox push: ") + hipGetErrorString(e);
+    *err = hip_error("inbox push", e);
     delete t;
     return nullptr;
   }
@@ -460,7 +441,7 @@ int push_poll(void* ticket, std::string* err) {
   hipError_t e = hipEventQuery(t->ev);
   if (e == hipSuccess) return 1;
   if (e == hipErrorNotReady) return 0;
-  *err = std::string("push failed: ") + hipGetErrorString(e);
+  *err = hip_error("push failed", e);
   return -1;
 }
 
@@ -485,6 +466,15 @@ struct UnpackTicket {
   std::vector<uint8_t*> bounces;          // per message, null = direct dst
   int n = 0;
 };
+
+// Return the results block and the bounces to the pool and delete the
+// ticket. sm_mu held; only once no kernel can write through the ticket.
+static void unpack_release(UnpackTicket* t) {
+  g_bounce_pool.put((uint8_t*)t->results);
+  for (auto* b : t->bounces)
+    if (b) g_bounce_pool.put(b);
+  delete t;
+}
 
 void* inbox_unpack(const InboxInfo& mine, const UnpackMsg* msgs, int n,
                    int lane, std::string* err) {
@@ -511,17 +501,14 @@ void* inbox_unpack(const InboxInfo& mine, const UnpackMsg* msgs, int n,
   args.spin_iters = spin;
   uint8_t* base = (uint8_t*)(uintptr_t)mine.base;
   for (int i = 0; i < n; i++) {
-    args.d[i].slot = base + (msgs[i].seq % mine.slots) * mine.slot_bytes;
+    args.d[i].slot = slot_of(mine, base, msgs[i].seq);
     args.d[i].seq = msgs[i].seq;
     args.d[i].size = msgs[i].size;
     uint8_t* dst = msgs[i].dst;
     if (!dst) {
       dst = g_bounce_pool.get();  // host recv: pinned staging
       if (!dst) {
-        g_bounce_pool.put((uint8_t*)t->results);
-        for (auto* b : t->bounces)
-          if (b) g_bounce_pool.put(b);
-        delete t;
+        unpack_release(t);
         *err = "pinned pool exhausted";
         return nullptr;
       }
@@ -534,11 +521,8 @@ void* inbox_unpack(const InboxInfo& mine, const UnpackMsg* msgs, int n,
   hipLaunchKernelGGL(k_inbox_unpack, dim3(n), dim3(256), 0, stream, args);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
-    *err = std::string("inbox unpack: ") + hipGetErrorString(e);
-    g_bounce_pool.put((uint8_t*)t->results);
-    for (auto* b : t->bounces)
-      if (b) g_bounce_pool.put(b);
-    delete t;
+    *err = hip_error("inbox unpack", e);
+    unpack_release(t);
     return nullptr;
   }
   return t;
@@ -559,12 +543,8 @@ const uint8_t* unpack_bounce(void* ticket, int idx) {
 }
 
 void unpack_free(void* ticket) {
-  UnpackTicket* t = (UnpackTicket*)ticket;
   std::lock_guard<std::mutex> lk(sm_mu);
-  g_bounce_pool.put((uint8_t*)t->results);
-  for (auto* b : t->bounces)
-    if (b) g_bounce_pool.put(b);
-  delete t;
+  unpack_release((UnpackTicket*)ticket);
 }
 
 // ---------------------------------------------------------------------------
@@ -597,8 +577,7 @@ static ArmTicket* arm_prepare(const InboxInfo& mine, uint64_t expect_seq,
   t->device = mine.device;
   static const unsigned spin =
       (unsigned)env_u64("STARWAY_ARM_SPIN", 8000);  // ~1 ms bound
-  a->slot = (const uint8_t*)(uintptr_t)mine.base +
-            (expect_seq % mine.slots) * mine.slot_bytes;
+  a->slot = slot_of(mine, (uint8_t*)(uintptr_t)mine.base, expect_seq);
   a->expect_seq = expect_seq;
   a->tag = tag;
   a->mask = mask;
@@ -618,7 +597,7 @@ static bool arm_launch(ArmTicket* t, const ArmArgs& a, int lane,
   hipLaunchKernelGGL(k_inbox_wait, dim3(1), dim3(256), 0, stream, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
-    *err = std::string("arm: ") + hipGetErrorString(e);
+    *err = hip_error("arm", e);
     g_flag_pool.put((uint8_t*)t->result);
     delete t;
     return false;
@@ -686,7 +665,7 @@ static bool ring_copy(const InboxInfo& ring, void* dst, const void* src,
   hipError_t e = on.status();
   if (e == hipSuccess) e = hipMemcpy(dst, src, n, kind);
   if (e != hipSuccess) {
-    *err = std::string(what) + ": " + hipGetErrorString(e);
+    *err = hip_error(what, e);
     return false;
   }
   return true;

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Copy-kernel microbench: bandwidth per size through sw::k_copy_b128[_nt].
+"""Copy-kernel microbench: bandwidth per size through sw::k_copy_b128<U, NT>.
 
 Used under rocprofv3 for kernel-trace/PMC evidence:
   rocprofv3 --kernel-trace --stats -d out -- python scripts/kernel_bench.py

@@ -1,5 +1,5 @@
 """Bit-exact, guard-banded tests of the accumulate kernels (k_accum_b128,
-k_accum_elem) and their dispatch (launch_accum_tuned), through the
+k_accum_elem) and their dispatch (launch_accum), through the
 synchronous hook ``_core._accum_sync``.
 
 Sizes are derived from the kernels' shape, as in tests/test_copy_kernels.py:

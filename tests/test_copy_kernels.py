@@ -26,9 +26,10 @@ from starway_amd import _core  # noqa: E402
 
 from _guard import GuardedCopy, Region  # noqa: E402
 
-HUGE = 1 << 62  # nt_threshold that no message reaches: plain k_copy_b128
+HUGE = 1 << 62  # nt_threshold that no message reaches: plain loads and stores
 
-# kernel id -> (nt_threshold, nt_unroll)
+# kernel id -> (nt_threshold, nt_unroll). The ids are the kernels' former
+# names: k_copy_b128<4, false>, <4, true> and <8, true>.
 KERNELS = {
     "k_copy_b128": (HUGE, 4),
     "k_copy_b128_nt": (1, 4),
@@ -77,7 +78,7 @@ def _kernel_cases():
 
 
 # =============================================================================
-# Contiguous, co-aligned: head (k_copy_b8) + 16 B bulk + tail (k_copy_b8)
+# Contiguous, co-aligned: head (k_copy_elem<1>) + 16 B bulk + tail (same)
 # =============================================================================
 
 
@@ -134,7 +135,7 @@ def test_default_tuning_capped_grid_nt():
 
 
 # =============================================================================
-# Contiguous, src and dst not co-aligned: k_copy_b32 / full-grid k_copy_b8
+# Contiguous, src and dst not co-aligned: k_copy_elem<4> / full-grid <1>
 # =============================================================================
 
 MISALIGNED_SIZES = [1, 4, 1023, 1024, 40_000]
@@ -149,7 +150,7 @@ def test_k_copy_b32_dword_coaligned(offs, nbytes):
     """4 B-co-aligned pointers, size a multiple of 4: the dword kernel.
     40 000 B at block_cap=2 is 10 000 dwords over a 512-lane grid."""
     _run_flat(3000 + nbytes + offs[1], offs[0], offs[1], nbytes,
-              f"k_copy_b32 {offs}", block_cap=2)
+              f"k_copy_elem<4> {offs}", block_cap=2)
 
 
 @pytest.mark.parametrize(
@@ -161,7 +162,7 @@ def test_k_copy_b8_full_grid(offs, nbytes):
     """Neither 16 B- nor dword-copyable: the byte kernel over a full grid
     (40 000 B at block_cap=2: 79 iterations per lane)."""
     _run_flat(3100 + nbytes + 16 * offs[0] + offs[1], offs[0], offs[1],
-              nbytes, f"k_copy_b8 {offs}", block_cap=2)
+              nbytes, f"k_copy_elem<1> {offs}", block_cap=2)
 
 
 @pytest.mark.parametrize("offs", [(0, 0), (5, 5), (0, 4), (1, 2)],
@@ -172,7 +173,7 @@ def test_zero_bytes_is_a_noop(offs):
 
 
 # =============================================================================
-# Strided: k_copy_strided_b128 (vec) / k_copy_strided_b8
+# Strided: k_copy_strided<16> (vec) / k_copy_strided<1>
 # =============================================================================
 
 
@@ -204,7 +205,7 @@ def test_k_copy_strided_b128(rows, row_bytes, layout, block_cap):
     _run_strided(4000 + rows * 7 + row_bytes,
                  Region(0, rows, row_bytes, ss),
                  Region(0, rows, row_bytes, ds),
-                 f"k_copy_strided_b128 rows={rows} rb={row_bytes} "
+                 f"k_copy_strided<16> rows={rows} rb={row_bytes} "
                  f"sstride={ss} dstride={ds} cap={block_cap}", block_cap)
 
 
@@ -218,7 +219,7 @@ def test_k_copy_strided_b8(rows, row_bytes, block_cap):
         _run_strided(4100 + rows * 7 + row_bytes + k,
                      Region(so, rows, row_bytes, ss),
                      Region(do, rows, row_bytes, ds),
-                     f"k_copy_strided_b8 rows={rows} rb={row_bytes} "
+                     f"k_copy_strided<1> rows={rows} rb={row_bytes} "
                      f"src+{so} dst+{do} cap={block_cap}", block_cap)
 
 
@@ -244,7 +245,7 @@ def test_strided_one_vec_condition_false(which):
     for block_cap in (0, 1):
         _run_strided(4200 + len(which), Region(so, 5, rb, ss),
                      Region(do, 5, rb, ds),
-                     f"k_copy_strided_b8 via {which} cap={block_cap}",
+                     f"k_copy_strided<1> via {which} cap={block_cap}",
                      block_cap)
 
 
@@ -271,6 +272,20 @@ MULTI_SPECS = [
 ]
 
 
+# The block copy's edge sizes through both of its branches (16 B vectors:
+# both pointers and the size multiples of 16; bytes: anything else), and a
+# 4 KiB message with either pointer one byte off 16 B alignment.
+MULTI_EDGE_SPECS = [
+    (16, 0, 0),        # one 16 B element: vector branch
+    (0, 1, 0),         # empty through the byte branch
+    (15, 0, 0),
+    (17, 0, 0),
+    (16, 0, 1),        # dst-only misaligned, a single element's worth
+    (4096, 1, 0),
+    (4096, 0, 1),
+]
+
+
 def _run_multi(specs, label):
     cases = [GuardedCopy(5000 + 31 * i + n, Region.flat(so, n),
                          Region.flat(do, n))
@@ -284,7 +299,7 @@ def _run_multi(specs, label):
 @pytest.mark.parametrize("n", [1, 3, 8])
 def test_k_copy_multi(n):
     if n == 1:
-        for spec in MULTI_SPECS:  # every descriptor kind alone
+        for spec in MULTI_SPECS + MULTI_EDGE_SPECS:  # every kind alone
             _run_multi([spec], "k_copy_multi n=1")
     else:
         _run_multi(MULTI_SPECS[:n], f"k_copy_multi n={n}")

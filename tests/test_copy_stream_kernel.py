@@ -62,7 +62,7 @@ def _scaled(n16):
 @pytest.mark.parametrize("n16", N16)
 def test_stream_two_blocks(n16):
     """stream_blocks=2, every bulk size crossed with byte offsets {0,1,15}
-    (head of 0, 15, 1 bytes through k_copy_b8) and tails {0,1,15}."""
+    (head of 0, 15, 1 bytes through k_copy_elem<1>) and tails {0,1,15}."""
     n = _scaled(n16)
     for k, (off, tail) in enumerate(itertools.product(OFFSETS, TAILS)):
         head = (16 - off) % 16

@@ -972,10 +972,10 @@ def _bytes(t):
 @pytest.mark.parametrize(
     "dtype,shape,cols",
     [
-        # 12 B column offset: misaligned rows, k_copy_strided_b8
+        # 12 B column offset: misaligned rows, k_copy_strided<1>
         pytest.param(torch.float32, (32, 64), (3, 35),
                      id="float32-k_copy_strided_b8"),
-        # 16 B column offset, 256 B stride: k_copy_strided_b128
+        # 16 B column offset, 256 B stride: k_copy_strided<16>
         pytest.param(torch.bfloat16, (24, 128), (8, 72),
                      id="bfloat16-k_copy_strided_b128"),
         pytest.param(torch.int64, (9, 40), (1, 33),
@@ -1025,7 +1025,7 @@ async def test_strided_elements_wider_than_a_byte(dtype, shape, cols):
 async def test_contiguous_send_to_strided_recv_above_inbox_size():
     """48 x 192 B (9216 B: cannot ride the ring) into frame[:, 37:229] of
     a 48 x 300 frame: contiguous source, strided destination, through the
-    pull kernel (column offset 37: k_copy_strided_b8). Gaps keep their
+    pull kernel (column offset 37: k_copy_strided<1>). Gaps keep their
     prefill."""
     case = GuardedCopy(7500, Region.flat(0, 48 * 192),
                        Region(37, 48, 192, 300))

@@ -282,6 +282,18 @@ def test_unpack_batched_with_missing_neighbours():
                 assert status == 1, label
                 assert staged is None
                 c.check(label)
+        # Two kinds the batch above does not hold: one 16 B element through
+        # the vector branch, and a full payload whose destination is one
+        # byte off 16 B alignment.
+        edge = [_case(31_000, 16), _case(31_001, ring.payload_max, dst_off=1)]
+        seqs = [base + 2 * s, base + 2 * s + 1]
+        _push(ring, [(c, q, 0xC000 + i)
+                     for i, (c, q) in enumerate(zip(edge, seqs))])
+        res = _core._inbox_unpack_sync(
+            ring, [(q, c.src.nbytes, c.dst_ptr) for c, q in zip(edge, seqs)])
+        assert res == [(1, None), (1, None)]
+        for c in edge:
+            c.check(f"unpack edge size={c.src.nbytes} dst+{c.dst.off}")
 
 
 # =============================================================================
