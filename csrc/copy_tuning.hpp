@@ -36,6 +36,12 @@ constexpr size_t kStreamNever = ~(size_t)0;
 // production uses; the hooks force one so tests and benches reach both.
 enum class CopyNdPath : int { Auto = 0, Generic = 1, Tiled = 2 };
 
+// Index arithmetic of k_copy_nd and k_copy_indexed. Auto is what production
+// uses: 32-bit wherever the granule count fits. Wide forces the 64-bit
+// instantiations, which Auto reaches only past 2^32 - 1 granules; the hooks
+// pass it so tests run them at every granule width on small messages.
+enum class IndexWidth : int { Auto = 0, Wide = 1 };
+
 // Environment-derived default (8192 blocks, 64 MiB, x4; streaming kernel
 // from 64 MiB, 8192 blocks; accumulate NT source loads from 192 MiB), read
 // once per process. Host-only: never

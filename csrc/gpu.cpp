@@ -672,7 +672,8 @@ static void log_route_once(int run_dev, const RtsDesc& rts, bool same_proc,
 static hipError_t copy_indexed(void* dst, const IndexRef& di, const void* src,
                                const IndexRef& si, uint64_t size, int run_dev,
                                hipStream_t stream, const CopyTuning& tuning,
-                               IndexUpload* up) {
+                               IndexUpload* up,
+                               IndexWidth width = IndexWidth::Auto) {
   if ((di.on() && di.count() * di.slice_bytes != size) ||
       (si.on() && si.count() * si.slice_bytes != size) || up->dev)
     return hipErrorInvalidValue;
@@ -697,7 +698,7 @@ static hipError_t copy_indexed(void* dst, const IndexRef& di, const void* src,
     if (e != hipSuccess) return e;
     s = IndexSide{(const uint32_t*)(base + nd), si.slice_bytes, si.stride};
   }
-  return launch_copy_indexed(dst, d, src, s, size, stream, tuning);
+  return launch_copy_indexed(dst, d, src, s, size, stream, tuning, width);
 }
 
 // Pack a device source of any geometry into fresh contiguous device staging
@@ -1089,8 +1090,8 @@ bool copy_strided_sync(void* dst, uint64_t dst_stride, const void* src,
 
 bool copy_nd_sync(void* dst, const Layout& dst_layout, const void* src,
                   const Layout& src_layout, uint64_t bytes, int device,
-                  size_t block_cap, CopyNdPath path, bool* ineligible,
-                  std::string* err) {
+                  size_t block_cap, CopyNdPath path, IndexWidth width,
+                  bool* ineligible, std::string* err) {
   CopyTuning t = resolve_tuning(CopyTuning{.block_cap = block_cap});
   *ineligible = path == CopyNdPath::Tiled &&
                 !copy_nd_tile_eligible(src_layout, dst_layout, src, dst);
@@ -1100,7 +1101,7 @@ bool copy_nd_sync(void* dst, const Layout& dst_layout, const void* src,
   }
   return run_sync(device, err, [&](hipStream_t stream) {
     return launch_copy_nd(dst, dst_layout, src, src_layout, bytes,
-                                stream, t, path);
+                                stream, t, path, width);
   });
 }
 
@@ -1110,12 +1111,12 @@ int copy_nd_tile_extent(int elem_bytes) {
 
 bool copy_index_sync(void* dst, const IndexRef& dst_index, const void* src,
                      const IndexRef& src_index, uint64_t bytes, int device,
-                     size_t block_cap, std::string* err) {
+                     size_t block_cap, IndexWidth width, std::string* err) {
   CopyTuning t = resolve_tuning(CopyTuning{.block_cap = block_cap});
   IndexUpload up;
   const bool ok = run_sync(device, err, [&](hipStream_t stream) {
     return copy_indexed(dst, dst_index, src, src_index, bytes, device, stream,
-                        t, &up);
+                        t, &up, width);
   });
   if (up.dev) {
     std::lock_guard<std::mutex> lk(g_mu);

@@ -22,11 +22,12 @@ bool copy_strided_sync(void* dst, uint64_t dst_stride, const void* src,
                        int device, size_t block_cap, std::string* err);
 // N-D copy (k_copy_nd / k_copy_nd_tile). Both layouts describe `bytes`
 // message bytes. *ineligible is set when path == Tiled was asked for a
-// pair outside the transpose family (nothing is launched then).
+// pair outside the transpose family (nothing is launched then). `width`
+// other than Auto forces k_copy_nd's 64-bit index instantiation.
 bool copy_nd_sync(void* dst, const Layout& dst_layout, const void* src,
                   const Layout& src_layout, uint64_t bytes, int device,
-                  size_t block_cap, CopyNdPath path, bool* ineligible,
-                  std::string* err);
+                  size_t block_cap, CopyNdPath path, IndexWidth width,
+                  bool* ineligible, std::string* err);
 // Tile extent (elements, both axes) of k_copy_nd_tile per element size;
 // a compile-time constant of the kernels, 0 for an unsupported size.
 int copy_nd_tile_extent(int elem_bytes);
@@ -35,7 +36,7 @@ int copy_nd_tile_extent(int elem_bytes);
 // uploaded on the pull stream ahead of the kernel, as in production.
 bool copy_index_sync(void* dst, const IndexRef& dst_index, const void* src,
                      const IndexRef& src_index, uint64_t bytes, int device,
-                     size_t block_cap, std::string* err);
+                     size_t block_cap, IndexWidth width, std::string* err);
 struct CopyDesc {
   void* dst;
   const void* src;

@@ -232,10 +232,11 @@ static void with_granule(uint64_t g, F&& f) {
 
 // Index type of a kernel that divides by quantities the count `n` bounds:
 // f(uint32_t{}) where every value fits, else f(uint64_t{}). 64-bit division
-// costs several times the 32-bit one on gfx950.
+// costs several times the 32-bit one on gfx950. Any width but Auto takes
+// the 64-bit form whatever the count (test hooks only).
 template <class F>
-static void with_index_width(uint64_t n, F&& f) {
-  if (n <= UINT32_MAX) f(uint32_t{});
+static void with_index_width(uint64_t n, IndexWidth width, F&& f) {
+  if (width == IndexWidth::Auto && n <= UINT32_MAX) f(uint32_t{});
   else f(uint64_t{});
 }
 
@@ -549,7 +550,7 @@ bool copy_nd_tile_eligible(const Layout& sl, const Layout& dl, const void* src,
 hipError_t launch_copy_nd(void* dst, const Layout& dl, const void* src,
                           const Layout& sl, uint64_t bytes,
                           hipStream_t stream, const CopyTuning& t,
-                          CopyNdPath path) {
+                          CopyNdPath path, IndexWidth width) {
   if (bytes == 0) return hipSuccess;
   bool s_is_src = false;
   int axis = -1;
@@ -608,7 +609,7 @@ hipError_t launch_copy_nd(void* dst, const Layout& dl, const void* src,
         // 32-bit index arithmetic only where every value fits: the granule
         // count bounds each quotient and (the message being non-empty) each
         // extent.
-        with_index_width(n, [&](auto idx) {
+        with_index_width(n, width, [&](auto idx) {
           hipLaunchKernelGGL((k_copy_nd<g(), decltype(idx)>), grid, dim3(256),
                              0, stream, sp, sl, dp, dl, n);
         });
@@ -676,7 +677,7 @@ __global__ __launch_bounds__(256) void k_copy_indexed(
 hipError_t launch_copy_indexed(void* dst, const IndexSide& ds,
                                const void* src, const IndexSide& ss,
                                uint64_t bytes, hipStream_t stream,
-                               const CopyTuning& t) {
+                               const CopyTuning& t, IndexWidth width) {
   if (bytes == 0) return hipSuccess;
   // Two dense sides are launch_copy's; an indexed side has whole, non-empty
   // slices that add up to the message.
@@ -693,7 +694,7 @@ hipError_t launch_copy_indexed(void* dst, const IndexSide& ds,
       [&](auto g) {
         const uint64_t n = bytes / g();
         const dim3 grid(copy_grid(n / 4 + 1, cap));
-        with_index_width(n, [&](auto idx) {
+        with_index_width(n, width, [&](auto idx) {
           hipLaunchKernelGGL((k_copy_indexed<g(), decltype(idx)>), grid,
                              dim3(256), 0, stream, sp, ss, dp, ds, n);
         });

@@ -48,7 +48,8 @@ hipError_t launch_copy_nd(void* dst, const Layout& dst_layout,
                           const void* src, const Layout& src_layout,
                           uint64_t bytes, hipStream_t stream,
                           const CopyTuning& t = default_copy_tuning(),
-                          CopyNdPath path = CopyNdPath::Auto);
+                          CopyNdPath path = CopyNdPath::Auto,
+                          IndexWidth width = IndexWidth::Auto);
 // Tile extent (elements, both axes) of k_copy_nd_tile per element size; 0
 // for an unsupported size.
 int copy_nd_tile_extent(int elem_bytes);
@@ -63,7 +64,8 @@ bool copy_nd_tile_eligible(const Layout& src_layout, const Layout& dst_layout,
 hipError_t launch_copy_indexed(void* dst, const IndexSide& dst_side,
                                const void* src, const IndexSide& src_side,
                                uint64_t bytes, hipStream_t stream,
-                               const CopyTuning& t = default_copy_tuning());
+                               const CopyTuning& t = default_copy_tuning(),
+                               IndexWidth width = IndexWidth::Auto);
 
 // dst[i] += src[i]; both pointers aligned to the element size, bytes a
 // multiple of it, no overlap.

@@ -30,6 +30,12 @@ CopyNdPath parse_copy_nd_path(const std::string& path) {
   throw py::value_error("copy_nd_sync: path must be auto, generic or tiled");
 }
 
+// wide_index of _copy_nd_sync and _copy_index_sync: the 64-bit index
+// kernels on a message of any size.
+IndexWidth index_width(bool wide) {
+  return wide ? IndexWidth::Wide : IndexWidth::Auto;
+}
+
 // One side of _copy_index_sync: None for a dense side.
 IndexRef hook_index_side(py::object index, uint64_t slice_bytes,
                          uint64_t stride, bool writable) {
@@ -225,8 +231,10 @@ void bind_hooks(py::module_& m) {
            const std::vector<int64_t>& dst_strides, uintptr_t src,
            const std::vector<uint64_t>& src_shape,
            const std::vector<int64_t>& src_strides, uint64_t itemsize,
-           int device, size_t block_cap, const std::string& path) {
+           int device, size_t block_cap, const std::string& path,
+           bool wide_index) {
           const CopyNdPath p = parse_copy_nd_path(path);
+          const IndexWidth w = index_width(wide_index);
           uint64_t dbytes = itemsize, sbytes = itemsize;
           for (uint64_t e : dst_shape) dbytes *= e;
           for (uint64_t e : src_shape) sbytes *= e;
@@ -240,7 +248,7 @@ void bind_hooks(py::module_& m) {
             bool ineligible = false;
             const bool ok = gpu::copy_nd_sync((void*)dst, dl, (const void*)src,
                                               sl, sbytes, device, block_cap, p,
-                                              &ineligible, err);
+                                              w, &ineligible, err);
             // Thrown with the GIL released: a plain C++ exception until
             // pybind11 translates it, by when the GIL is held again.
             if (ineligible) throw py::value_error("copy_nd_sync: " + *err);
@@ -250,7 +258,7 @@ void bind_hooks(py::module_& m) {
         py::arg("dst"), py::arg("dst_shape"), py::arg("dst_strides"),
         py::arg("src"), py::arg("src_shape"), py::arg("src_strides"),
         py::arg("itemsize"), py::arg("device"), py::arg("block_cap") = 0,
-        py::arg("path") = "auto");
+        py::arg("path") = "auto", py::arg("wide_index") = false);
   // Indexed buffers (index.hpp). _plan_index, _index_offset and the two
   // descriptor hooks are host-only and work without a GPU.
   m.attr("_INDEX_MAX") = kIndexMax;
@@ -301,11 +309,12 @@ void bind_hooks(py::module_& m) {
         py::arg("payload"), py::arg("size"));
   // One k_copy_indexed launch on raw device pointers; None for a dense
   // side. The arguments are checked before any device is touched.
+  // wide_index runs the 64-bit index kernel whatever the message size.
   m.def("_copy_index_sync",
         [](uintptr_t dst, py::object dst_index, uint64_t dst_slice,
            uint64_t dst_stride, uintptr_t src, py::object src_index,
            uint64_t src_slice, uint64_t src_stride, uint64_t bytes, int device,
-           size_t block_cap) {
+           size_t block_cap, bool wide_index) {
           if (dst_index.is_none() && src_index.is_none())
             throw py::value_error("copy_index_sync: both sides are dense "
                                   "(that is _copy_device_sync's)");
@@ -324,12 +333,14 @@ void bind_hooks(py::module_& m) {
                 std::to_string(si.count() * src_slice) + " B, message " +
                 std::to_string(bytes));
           released("copy_index_sync", gpu::copy_index_sync, (void*)dst, di,
-                   (const void*)src, si, bytes, device, block_cap);
+                   (const void*)src, si, bytes, device, block_cap,
+                   index_width(wide_index));
         },
         py::arg("dst"), py::arg("dst_index"), py::arg("dst_slice"),
         py::arg("dst_stride"), py::arg("src"), py::arg("src_index"),
         py::arg("src_slice"), py::arg("src_stride"), py::arg("bytes"),
-        py::arg("device"), py::arg("block_cap") = 0);
+        py::arg("device"), py::arg("block_cap") = 0,
+        py::arg("wide_index") = false);
   // Tile extents of k_copy_nd_tile: element bytes -> (T_A, T_B) elements.
   {
     py::dict tiles;

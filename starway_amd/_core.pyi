@@ -197,11 +197,13 @@ def _copy_nd_sync(
     dst: int, dst_shape: list[int], dst_strides: list[int],
     src: int, src_shape: list[int], src_strides: list[int],
     itemsize: int, device: int, block_cap: int = 0, path: str = "auto",
+    wide_index: bool = False,
 ) -> None:
     """Run the N-D copy kernels synchronously on raw device pointers
     (strides in bytes). path: "auto" (the production dispatch), "generic"
     (k_copy_nd) or "tiled" (k_copy_nd_tile; ValueError when the pair is not
-    in the transpose family)."""
+    in the transpose family). wide_index runs k_copy_nd's 64-bit index
+    instantiation, which production takes only past 2**32 - 1 granules."""
 
 # k_copy_nd_tile tile extents: element bytes -> (T_A, T_B) in elements.
 _ND_TILE: dict[int, tuple[int, int]]
@@ -234,11 +236,13 @@ def _index_desc_decode(payload: bytes, size: int) -> tuple[list[int], int, int]:
 def _copy_index_sync(
     dst: int, dst_index: list[int] | None, dst_slice: int, dst_stride: int,
     src: int, src_index: list[int] | None, src_slice: int, src_stride: int,
-    bytes: int, device: int, block_cap: int = 0,
+    bytes: int, device: int, block_cap: int = 0, wide_index: bool = False,
 ) -> None:
     """One k_copy_indexed launch on raw device pointers, synchronous; None
     for a dense side. ValueError, before any device is touched, for two
-    dense sides or slices that do not multiply out to `bytes`."""
+    dense sides or slices that do not multiply out to `bytes`. wide_index
+    runs the 64-bit index instantiation, which production takes only past
+    2**32 - 1 granules."""
 
 # Test hooks for the small-message kernels (csrc/smallmsg.hip). They call the
 # host functions the engine calls; every wait has a host deadline of ~2 s.

@@ -17,21 +17,22 @@ from _guard_index import GuardedIndex, Pool, dense  # noqa: E402
 CAPS = [0, 1]
 
 
-def run(case: GuardedIndex, cap: int, label: str):
-    _core._copy_index_sync(*case.hook_args(), 0, cap)
-    case.check(f"{label} cap={cap}")
+def run(case: GuardedIndex, cap: int, label: str, wide_index: bool = False):
+    _core._copy_index_sync(*case.hook_args(), 0, cap, wide_index=wide_index)
+    case.check(f"{label} cap={cap} wide_index={wide_index}")
 
 
-def both_ways(seed: int, pool: Pool, cap: int, label: str, flat_off: int = 0):
+def both_ways(seed: int, pool: Pool, cap: int, label: str, flat_off: int = 0,
+              wide_index: bool = False):
     """Gather pool[idx] into a dense run, and scatter a dense run into it.
     A source may repeat an entry; the scatter then takes the list without
     the repeat."""
     run(GuardedIndex(seed, pool, dense(flat_off, pool.nbytes)), cap,
-        f"{label} gather")
+        f"{label} gather", wide_index)
     uniq = tuple(dict.fromkeys(pool.index))
     spool = Pool(pool.off, pool.slices, pool.slice_bytes, pool.pitch, uniq)
     run(GuardedIndex(seed + 100, dense(flat_off, spool.nbytes), spool), cap,
-        f"{label} scatter")
+        f"{label} scatter", wide_index)
 
 
 # (label, pool, offset of the dense side): arenas are 256 B aligned, so the
@@ -62,14 +63,33 @@ def test_gather_and_scatter(label, pool, flat_off, cap):
 
 
 @pytest.mark.parametrize("cap", CAPS)
+@pytest.mark.parametrize("label,pool,flat_off", GRANULES,
+                         ids=[g[0] for g in GRANULES])
+def test_gather_and_scatter_wide_index(label, pool, flat_off, cap):
+    """k_copy_indexed<G, uint64_t>, which production reaches only past
+    2**32 - 1 granules: the same table, forced by the hook."""
+    both_ways(10 + GRANULES.index((label, pool, flat_off)), pool, cap, label,
+              flat_off, wide_index=True)
+
+
+def interleave(cap, wide_index):
+    src = Pool(0, 9, 768, 784, (8, 0, 4, 5, 2, 7))
+    dst = Pool(16, 7, 1152, 1168, (6, 0, 3, 5))
+    assert src.nbytes == dst.nbytes == 4608
+    run(GuardedIndex(30, src, dst), cap, "indexed -> indexed", wide_index)
+
+
+@pytest.mark.parametrize("cap", CAPS)
 def test_indexed_to_indexed_boundaries_interleave(cap):
     """Six 768 B source slices into four 1152 B destination slices: every
     destination slice is fed by two source slices and every second source
     slice is split over two destination slices."""
-    src = Pool(0, 9, 768, 784, (8, 0, 4, 5, 2, 7))
-    dst = Pool(16, 7, 1152, 1168, (6, 0, 3, 5))
-    assert src.nbytes == dst.nbytes == 4608
-    run(GuardedIndex(30, src, dst), cap, "indexed -> indexed")
+    interleave(cap, wide_index=False)
+
+
+@pytest.mark.parametrize("cap", CAPS)
+def test_indexed_to_indexed_boundaries_interleave_wide_index(cap):
+    interleave(cap, wide_index=True)
 
 
 @pytest.mark.parametrize("cap", CAPS)

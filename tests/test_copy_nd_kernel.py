@@ -120,13 +120,28 @@ def granule_views(which, g):
     "which,g", [(None, 16)] + list(itertools.product(QUANTITIES,
                                                      [8, 4, 2, 1])))
 def test_generic_every_granule(which, g, cap):
+    every_granule(which, g, cap, wide_index=False)
+
+
+def every_granule(which, g, cap, wide_index):
     src, dst = granule_views(which, g)
     case = GuardedNd(400 + 8 * QUANTITIES.index(which or "src_ptr") + g,
                      src, dst)
     assert _core._plan_granule(plan(src), plan(dst, True), case.src_ptr,
                                case.dst_ptr) == g
-    _core._copy_nd_sync(*case.hook_args(), 0, block_cap=cap, path="generic")
-    case.check(f"granule {g} forced by {which}")
+    _core._copy_nd_sync(*case.hook_args(), 0, block_cap=cap, path="generic",
+                        wide_index=wide_index)
+    case.check(f"granule {g} forced by {which}, wide_index={wide_index}")
+
+
+@pytest.mark.parametrize("cap", [1, 2])
+@pytest.mark.parametrize(
+    "which,g", [(None, 16)] + list(itertools.product(QUANTITIES,
+                                                     [8, 4, 2, 1])))
+def test_generic_every_granule_wide_index(which, g, cap):
+    """k_copy_nd<G, uint64_t>, which production reaches only past 2**32 - 1
+    granules (64 GiB at G = 16): the same cases, forced by the hook."""
+    every_granule(which, g, cap, wide_index=True)
 
 
 @pytest.mark.parametrize("cap", [1, 2])
