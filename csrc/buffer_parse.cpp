@@ -179,6 +179,49 @@ void apply_reduce(BufferRef& ref, const std::string& reduce,
   ref.elem = et;
 }
 
+// recv(msg_dtype=...): the element type of the message, when it is not the
+// buffer's own. Every refusal is a ValueError whose text starts with
+// "msg_dtype limit:". The name is checked before the buffer is looked at;
+// everything else against the parsed buffer, after apply_reduce.
+py::value_error msg_dtype_limit(const std::string& what) {
+  return py::value_error("msg_dtype limit: " + what);
+}
+
+bool float_elem(ElemType t) {
+  return t == ElemType::F32 || t == ElemType::F16 || t == ElemType::BF16;
+}
+
+void check_msg_dtype(const std::string& msg_dtype) {
+  if (!msg_dtype.empty() && !float_elem(parse_elem_type(msg_dtype)))
+    throw msg_dtype_limit("unsupported message dtype '" + msg_dtype +
+                          "' (supported: float32, float16, bfloat16)");
+}
+
+void apply_msg_dtype(BufferRef& ref, const std::string& msg_dtype,
+                     const std::string& dtype) {
+  if (msg_dtype.empty()) return;
+  if (ref.device < 0)
+    throw msg_dtype_limit(
+        "host buffers are not supported (device tensors only)");
+  const ElemType et = parse_elem_type(dtype);
+  if (!float_elem(et))
+    throw msg_dtype_limit("unsupported buffer dtype '" + dtype +
+                          "' (supported: float32, float16, bfloat16)");
+  const ElemType mt = parse_elem_type(msg_dtype);
+  // The buffer's own type: today's receive, plain or reducing.
+  if (mt == et) return;
+  if (!ref.dense())
+    throw msg_dtype_limit(
+        "the destination must be contiguous (strided and N-D views are not "
+        "supported)");
+  if ((uintptr_t)ref.ptr % elem_size(et))
+    throw msg_dtype_limit("the destination must be aligned to its item "
+                          "size (" +
+                          std::to_string(elem_size(et)) + " B)");
+  ref.elem = et;
+  ref.msg_elem = mt;
+}
+
 // index= of send/recv: a host-side list of slice numbers along the
 // buffer's first dimension (index.hpp). Every refusal is a ValueError whose
 // text starts with "index limit:".
@@ -316,13 +359,19 @@ std::shared_ptr<const IndexList> parse_index(py::object index, uint64_t extent,
 
 BufferRef parse_message_buffer(py::handle buffer, py::object index,
                                bool writable, const std::string& reduce,
-                               const std::string& dtype) {
+                               const std::string& dtype,
+                               const std::string& msg_dtype) {
   check_reduce_op(reduce);
+  check_msg_dtype(msg_dtype);
   if (index.is_none()) {
     BufferRef ref = parse_buffer(buffer, writable);
     apply_reduce(ref, reduce, dtype);
+    apply_msg_dtype(ref, msg_dtype, dtype);
     return ref;
   }
+  if (!msg_dtype.empty())
+    throw msg_dtype_limit("index= cannot be combined with msg_dtype= (a "
+                          "converting destination stays contiguous)");
   if (!reduce.empty())
     throw index_limit("index= cannot be combined with reduce= (a reducing "
                       "destination stays contiguous)");

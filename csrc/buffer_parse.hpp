@@ -1,6 +1,6 @@
 // Python object -> BufferRef: what send and recv do with their buffer,
-// index=, reduce= and dtype= arguments (buffer_parse.cpp). The test hooks
-// reuse the index and dtype parsers.
+// index=, reduce=, dtype= and msg_dtype= arguments (buffer_parse.cpp). The
+// test hooks reuse the index and dtype parsers.
 #pragma once
 
 #include "core.hpp"
@@ -18,6 +18,7 @@ std::shared_ptr<const IndexList> parse_index(py::object index, uint64_t extent,
 // The buffer of a send (reduce empty) or recv, with or without index=.
 BufferRef parse_message_buffer(py::handle buffer, py::object index,
                                bool writable, const std::string& reduce = "",
-                               const std::string& dtype = "");
+                               const std::string& dtype = "",
+                               const std::string& msg_dtype = "");
 
 }  // namespace sw

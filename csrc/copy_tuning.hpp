@@ -8,6 +8,22 @@
 
 namespace sw {
 
+// Lane shape of the convert kernels for a 2-byte <-> 4-byte pair
+// (kernels.hip "Convert family"): A is 8 elements per lane, B is 4.
+// Default is what production runs.
+enum class ConvertShape : int { Default = 0, A = 1, B = 2 };
+
+// How the convert dispatch splits a message of n elements: `head` elements
+// by the element kernel, `vectors` lanes of `lane_elems` elements by the
+// vector kernel, `tail` elements by the element kernel; or, when no head
+// co-aligns the two sides, everything by the element kernel (elem_only,
+// tail == n).
+struct ConvertPlan {
+  bool elem_only;
+  int lane_elems;
+  size_t head, vectors, tail;
+};
+
 struct CopyTuning {
   size_t block_cap;     // max workgroups per launch (STARWAY_COPY_BLOCKS)
   size_t nt_threshold;  // bulk bytes at/above which the non-temporal kernels
@@ -23,6 +39,8 @@ struct CopyTuning {
   // SOURCE loads are non-temporal (STARWAY_ACCUM_NT_THRESHOLD). Its own
   // knob: the read-modify-write kernel crosses over far above the copies.
   size_t accum_nt_threshold = 0;
+  // Convert kernels (converting receive): the lane shape, hooks only.
+  ConvertShape convert_shape = ConvertShape::Default;
 };
 
 // Messages per batched small-message copy (k_copy_multi, begin_pull_multi):

@@ -194,6 +194,12 @@ struct BufferRef {
   // on a dense device buffer whose ptr is aligned to the element size.
   ReduceOp reduce = ReduceOp::None;
   ElemType elem = ElemType::None;
+  // Converting receive (recv side only): the message holds elements of
+  // `msg_elem`, the buffer elements of `elem` (set for a converting receive
+  // whether it reduces or not), and the two differ. Delivery converts, or
+  // adds in fp32 and rounds once when reducing. Same buffer limits as a
+  // reducing receive.
+  ElemType msg_elem = ElemType::None;
   // One dense run of `size` bytes at ptr. Anything else is packed or
   // unpacked by a copy kernel: it stays off the inbox push plane and the
   // doorbell, takes the bounce path for eager/inbox/CMA deliveries and
@@ -202,18 +208,32 @@ struct BufferRef {
   // Whether a message of `len` bytes fits this receive buffer: not longer
   // than it, and exactly its size unless it is dense (a strided window
   // filled in part would smear partial rows).
+  // A converting buffer holds size / itemsize elements and takes a message
+  // of no more elements than that, counted in the message's element size.
   bool accepts(uint64_t len) const {
+    if (converting())
+      return len / elem_size(msg_elem) <= size / elem_size(elem);
     return len <= size && (dense() || len == size);
   }
   bool reducing() const { return reduce != ReduceOp::None; }
-  // Dense, and delivery overwrites: only such a device buffer may be
-  // written by a copy that does not go through begin_pull or begin_h2d
-  // (k_copy_multi, the inbox unpack kernel, the doorbell). A reducing
-  // buffer is delivered through those two alone: they accumulate.
-  bool plain() const { return dense() && !reducing(); }
-  // A reducing receive takes whole elements only.
+  bool converting() const { return msg_elem != ElemType::None; }
+  // The element type a message is read as: the buffer's own unless the
+  // receive converts. None for a plain receive.
+  ElemType msg_type() const { return converting() ? msg_elem : elem; }
+  // The longest message accepts() takes, in message bytes.
+  uint64_t capacity() const {
+    return converting() ? size / elem_size(elem) * elem_size(msg_elem) : size;
+  }
+  // Dense, and delivery overwrites with the message's own bytes: only such
+  // a device buffer may be written by a copy that does not go through
+  // begin_pull or begin_h2d (k_copy_multi, the inbox unpack kernel, the
+  // doorbell). A reducing or converting buffer is delivered through those
+  // two alone: they accumulate and convert.
+  bool plain() const { return dense() && !reducing() && !converting(); }
+  // A reducing or converting receive takes whole elements only.
   bool whole_elems(uint64_t len) const {
-    return !reducing() || len % elem_size(elem) == 0;
+    return (!reducing() && !converting()) ||
+           len % elem_size(msg_type()) == 0;
   }
   // This buffer as a Layout, for a copy whose other side is N-D. Never
   // asked of an indexed buffer: no Layout describes one.
@@ -493,6 +513,9 @@ class Engine {
     std::atomic<uint64_t> doorbell_rx{0};            // of inbox_rx, pre-armed
     // Delivered reducing receives; each also counts on its plane.
     std::atomic<uint64_t> reduce_rx{0};
+    // Delivered converting receives (msg_dtype other than the buffer's);
+    // each also counts on its plane, and in reduce_rx when reducing.
+    std::atomic<uint64_t> cast_rx{0};
     // Messages sent from / delivered into an indexed buffer.
     std::atomic<uint64_t> index_tx{0}, index_rx{0};
     std::atomic<uint64_t> unexpected_rx{0};
@@ -771,7 +794,9 @@ bool make_rts(const BufferRef& buf, RtsDesc* out, std::string* err);
 // Begin an async pull of `size` bytes described by `rts` into dst (host or
 // device). Returns an opaque ticket (hipEvent) or null on error. A reducing
 // dst is accumulated into (k_accum_*), on lane 0 of its device whatever the
-// source; STARWAY_PULL=sdma does not apply to it. src_index is the source's
+// source; STARWAY_PULL=sdma does not apply to it. A converting dst goes the
+// same way through the convert kernels (k_convert_*), on lane 0 only when
+// it also reduces. src_index is the source's
 // index list when the descriptor came in an FT_RTS_INDEXED frame (rts then
 // describes the pool's base), off otherwise.
 void* begin_pull(const RtsDesc& rts, const IndexRef& src_index,

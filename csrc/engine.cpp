@@ -808,6 +808,8 @@ void Engine::deliver_recv(Op* r, uint64_t tag, uint64_t len, RxPlane plane) {
   }
   if (r->buf.reducing())
     stats_.reduce_rx.fetch_add(1, std::memory_order_relaxed);
+  if (r->buf.converting())
+    stats_.cast_rx.fetch_add(1, std::memory_order_relaxed);
   if (r->buf.index.on() && plane != RxPlane::None)
     stats_.index_rx.fetch_add(1, std::memory_order_relaxed);
   Completion comp;

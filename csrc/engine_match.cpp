@@ -21,6 +21,10 @@ std::string truncated_msg(uint64_t len, uint64_t cap) {
 }
 
 std::string reduce_len_msg(uint64_t len, const BufferRef& buf) {
+  if (buf.converting())
+    return "msg_dtype: message length " + std::to_string(len) +
+           " B is not a multiple of the message's item size (" +
+           std::to_string(elem_size(buf.msg_elem)) + " B)";
   return "reduce: message length " + std::to_string(len) +
          " B is not a multiple of the item size (" +
          std::to_string(elem_size(buf.elem)) + " B)";
@@ -167,7 +171,8 @@ void Engine::complete_recv_from_unexpected(Op* op, UnexpectedMsg* um) {
     return;
   }
   if (!op->buf.accepts(um->size)) {
-    fail_op(op, "receive failed: " + truncated_msg(um->size, op->buf.size));
+    fail_op(op, "receive failed: " +
+                    truncated_msg(um->size, op->buf.capacity()));
     return;
   }
   if (!op->buf.whole_elems(um->size)) {

@@ -37,7 +37,7 @@ void Engine::start_gpu_pull(Op* recv_op, const RtsDesc& rts,
   // this plane have always seen, not the truncation text.
   const BufferRef& buf = recv_op->buf;
   if (!buf.accepts(size) && !(buf.rows > 0 && size < buf.size)) {
-    reject_rndv(c, sender_op, recv_op, truncated_msg(size, buf.size));
+    reject_rndv(c, sender_op, recv_op, truncated_msg(size, buf.capacity()));
     return;
   }
   if (!buf.whole_elems(size)) {
@@ -151,7 +151,7 @@ void Engine::inbox_release_seq(Connection* c, uint64_t seq) {
 void Engine::dispatch_smsg_to_recv(Connection* c, Op* r, uint64_t tag,
                                    uint64_t size, uint64_t seq) {
   if (!r->buf.accepts(size)) {
-    fail_op(r, "receive failed: " + truncated_msg(size, r->buf.size));
+    fail_op(r, "receive failed: " + truncated_msg(size, r->buf.capacity()));
     inbox_release_seq(c, seq);  // discard without reading the slot
     return;
   }
@@ -411,9 +411,11 @@ void Engine::progress_unpacks(bool& did_work) {
             // counts as what it is, once, when it is delivered: inbox_rx.
             // (A plain strided / other-device recv on this path has always
             // counted as gpu_rx, and still does.)
+            // A converting recv is one of those, reducing or not.
+            const BufferRef& rb = m.recv_op->buf;
             upload_to_recv(m.recv_op, m.tag, m.size, std::move(heap),
-                           m.recv_op->buf.reducing() ? RxPlane::Inbox
-                                                     : RxPlane::Gpu);
+                           rb.reducing() || rb.converting() ? RxPlane::Inbox
+                                                            : RxPlane::Gpu);
           }
           inbox_release_seq(m.conn, m.seq);
           continue;
@@ -506,7 +508,8 @@ void Engine::start_cma_pull(Op* recv_op, const CmaDesc& cma, uint64_t tag,
                             uint64_t size, uint64_t sender_op,
                             Connection* c) {
   if (!recv_op->buf.accepts(size)) {
-    reject_rndv(c, sender_op, recv_op, truncated_msg(size, recv_op->buf.size));
+    reject_rndv(c, sender_op, recv_op,
+                truncated_msg(size, recv_op->buf.capacity()));
     return;
   }
   if (!recv_op->buf.whole_elems(size)) {

@@ -969,7 +969,7 @@ void Engine::finish_eager_into_recv(Connection* c) {
       const bool fits = r->buf.accepts(r->recv_len);
       fail_op(r, "receive failed: " +
                      (fits ? reduce_len_msg(r->recv_len, r->buf)
-                           : truncated_msg(r->recv_len, r->buf.size)));
+                           : truncated_msg(r->recv_len, r->buf.capacity())));
       return;
     }
     if (r->buf.device >= 0) {

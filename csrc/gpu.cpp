@@ -564,15 +564,17 @@ static Ticket* finish_ticket(int device, hipStream_t stream, void* staging,
   return t;
 }
 
-// A reducing destination takes whole, aligned elements into a dense buffer.
+// A reducing or converting destination takes whole elements, read in the
+// message's element size, into a dense buffer aligned to its own.
 static bool check_reduce_dst(const BufferRef& dst, uint64_t size,
                              std::string* err) {
   const size_t es = elem_size(dst.elem);
-  if (dst.dense() && es != 0 && (uintptr_t)dst.ptr % es == 0 &&
-      size % es == 0 && size <= dst.size)
+  const size_t ms = elem_size(dst.msg_type());
+  if (dst.dense() && es != 0 && ms != 0 && (uintptr_t)dst.ptr % es == 0 &&
+      size % ms == 0 && size / ms <= dst.size / es)
     return true;
-  *err = "reduce: destination or message length does not fit the "
-         "element type";
+  *err = std::string(dst.converting() ? "msg_dtype" : "reduce") +
+         ": destination or message length does not fit the element type";
   return false;
 }
 
@@ -752,20 +754,33 @@ static hipError_t download(void* host_dst, const BufferRef& src, int run_dev,
                         stream);
 }
 
-// dst += source, on `stream`. The accumulate kernel reads an element-
-// aligned contiguous source where it lies (peer memory over xGMI,
-// hipIpc-mapped, or local); a rows, N-D, indexed or element-misaligned
-// source is packed into staging first (same stream, so in order).
+// `size` message bytes at `from`, aligned to the message's element size,
+// into a reducing or converting dst: the accumulate kernels for a message
+// of the buffer's own type, the convert kernels for another.
+static hipError_t launch_typed(const BufferRef& dst, const void* from,
+                               uint64_t size, hipStream_t stream) {
+  if (dst.converting())
+    return launch_convert(dst.ptr, dst.elem, from, dst.msg_elem,
+                          size / elem_size(dst.msg_elem), dst.reducing(),
+                          stream);
+  return launch_accum(dst.ptr, from, size, dst.elem, stream);
+}
+
+// dst += source (reducing), dst = convert(source) (converting) or both, on
+// `stream`. The kernel reads an element-aligned contiguous source where it
+// lies (peer memory over xGMI, hipIpc-mapped, or local); a rows, N-D,
+// indexed or element-misaligned source is packed into staging first (same
+// stream, so in order).
 static hipError_t accumulate(const BufferRef& dst, const BufferRef& src,
                              int run_dev, hipStream_t stream, void** staging,
                              IndexUpload* up) {
   const void* from = src.ptr;
-  if (!src.dense() || (uintptr_t)src.ptr % elem_size(dst.elem) != 0) {
+  if (!src.dense() || (uintptr_t)src.ptr % elem_size(dst.msg_type()) != 0) {
     hipError_t e = pack_to_staging(src, run_dev, stream, staging, up);
     if (e != hipSuccess) return e;
     from = *staging;
   }
-  return launch_accum(dst.ptr, from, src.size, dst.elem, stream);
+  return launch_typed(dst, from, src.size, stream);
 }
 
 // One side of an N-D copy of `size` message bytes, as a Layout.
@@ -862,6 +877,8 @@ static bool copy_d2d(const BufferRef& dst, const PullSrc& from, uint64_t size,
 //             packed into device staging first
 //   reducing  accumulate(): k_accum_* from the source where it lies, or
 //             from staging (rows, N-D, element-misaligned source)
+//   converting  accumulate() as well, ending in k_convert_*; on lane 0
+//             only when it also reduces
 //   device    copy_d2d(): one copy kernel (or SDMA) per geometry pair
 void* begin_pull(const RtsDesc& rts, const IndexRef& src_index,
                  const BufferRef& dst, uint64_t size, std::string* err) {
@@ -896,8 +913,10 @@ void* begin_pull(const RtsDesc& rts, const IndexRef& src_index,
   } else {
     if (src.same_proc) ensure_peer_access(dst.device, rts.device);
     log_route_once(run_dev, rts, src.same_proc, lane,
-                   dst.reducing() ? "gfx950_accum" : "gfx950_copy");
-    if (dst.reducing()) {
+                   dst.converting() ? "gfx950_convert"
+                   : dst.reducing() ? "gfx950_accum"
+                                    : "gfx950_copy");
+    if (dst.reducing() || dst.converting()) {
       if (!check_reduce_dst(dst, size, err)) return nullptr;
       e = accumulate(dst, src.buf, run_dev, stream, &staging, &up);
     } else {
@@ -956,12 +975,11 @@ void* begin_h2d(const BufferRef& dst, const void* src, uint64_t size,
   hipError_t e = hipSuccess;
   void* staging = nullptr;
   IndexUpload up;
-  if (dst.reducing()) {
+  if (dst.reducing() || dst.converting()) {
     if (!check_reduce_dst(dst, size, err)) return nullptr;
     if (size > 0) {
       e = stage_from_host(src, size, stream, &staging);
-      if (e == hipSuccess)
-        e = launch_accum(dst.ptr, staging, size, dst.elem, stream);
+      if (e == hipSuccess) e = launch_typed(dst, staging, size, stream);
     }
   } else if (!check_window(dst, size, err)) {
     return nullptr;
@@ -1137,6 +1155,28 @@ bool accum_sync(void* dst, const void* src, size_t nbytes, ElemType dtype,
   return run_sync(device, err, [&](hipStream_t stream) {
     return launch_accum(dst, src, nbytes, dtype, stream, t);
   });
+}
+
+bool convert_sync(void* dst, ElemType dst_type, const void* src,
+                  ElemType src_type, size_t n_elems, bool accumulate,
+                  int device, const CopyTuning& tuning, std::string* err) {
+  CopyTuning t = resolve_tuning(tuning);
+  t.convert_shape = tuning.convert_shape;
+  return run_sync(device, err, [&](hipStream_t stream) {
+    return launch_convert(dst, dst_type, src, src_type, n_elems, accumulate,
+                          stream, t);
+  });
+}
+
+ConvertPlan convert_plan(uintptr_t dst, ElemType dst_type, uintptr_t src,
+                         ElemType src_type, size_t n_elems,
+                         ConvertShape shape) {
+  return sw::convert_plan(dst, dst_type, src, src_type, n_elems, shape);
+}
+
+ConvertShape convert_default_shape() { return sw::convert_default_shape(); }
+void set_convert_default_shape(ConvertShape shape) {
+  sw::set_convert_default_shape(shape);
 }
 
 // Callers validate 1 <= n <= kMultiMax and bytes < 2^32 (launch_copy_multi does not).

@@ -49,6 +49,21 @@ bool copy_multi_sync(const CopyDesc* descs, int n, int device,
 // are not multiples of the element size.
 bool accum_sync(void* dst, const void* src, size_t nbytes, ElemType dtype,
                 int device, const CopyTuning& tuning, std::string* err);
+// The convert kernels (launch_convert): dst[i] = dst_type(src[i]), or with
+// `accumulate` dst_type(float(dst[i]) + float(src[i])), over n_elems
+// elements. tuning.convert_shape picks the lane shape. The caller has
+// checked the types and each pointer's alignment to its element size.
+bool convert_sync(void* dst, ElemType dst_type, const void* src,
+                  ElemType src_type, size_t n_elems, bool accumulate,
+                  int device, const CopyTuning& tuning, std::string* err);
+// launch_convert's split of such a message (kernels.hpp); host only.
+ConvertPlan convert_plan(uintptr_t dst, ElemType dst_type, uintptr_t src,
+                         ElemType src_type, size_t n_elems,
+                         ConvertShape shape);
+// The lane shape production launches run, and a bench's override of it
+// (Default restores the production shape). Host only.
+ConvertShape convert_default_shape();
+void set_convert_default_shape(ConvertShape shape);
 
 // The inbox kernels (smallmsg.hip). These drive the kernels through the
 // host functions the engine uses (same-process push, lane 0) and wait

@@ -25,6 +25,7 @@
 //    of HBM traffic (docs/benchmark.md "Streaming copy").
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdint>
 #include <cstdlib>
 #include <type_traits>
@@ -718,10 +719,23 @@ using f32x2 = __attribute__((ext_vector_type(2))) float;
 using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
 using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
 
-// One tag per element type: W is the element's storage word, add() works
-// on one element, add32() on the 32-bit word of a 16 B vector.
+// One tag per element type: W is the element's storage word. up() / down()
+// take one element to fp32 and back (down rounds to nearest even); widen()
+// / narrow() do the same for the kPerWord elements packed in one 32-bit
+// word of a vector. add() works on one element, add32() on one such word.
 struct AccF32 {
   using W = uint32_t;
+  static constexpr int kPerWord = 1;
+  static __device__ __forceinline__ float up(W w) { return __uint_as_float(w); }
+  static __device__ __forceinline__ W down(float f) {
+    return __float_as_uint(f);
+  }
+  static __device__ __forceinline__ void widen(uint32_t w, float* f) {
+    f[0] = __uint_as_float(w);
+  }
+  static __device__ __forceinline__ uint32_t narrow(const float* f) {
+    return __float_as_uint(f[0]);
+  }
   static __device__ __forceinline__ W add(W d, W s) {
     return __float_as_uint(__uint_as_float(d) + __uint_as_float(s));
   }
@@ -740,33 +754,69 @@ struct AccI32 {
 
 struct AccF16 {
   using W = uint16_t;
+  static constexpr int kPerWord = 2;
+  static __device__ __forceinline__ float up(W w) {
+    return (float)__builtin_bit_cast(_Float16, w);
+  }
+  static __device__ __forceinline__ W down(float f) {
+    return __builtin_bit_cast(W, (_Float16)f);
+  }
+  static __device__ __forceinline__ void widen(uint32_t w, float* f) {
+    const f32x2 v =
+        __builtin_convertvector(__builtin_bit_cast(f16x2, w), f32x2);
+    f[0] = v.x;
+    f[1] = v.y;
+  }
+  static __device__ __forceinline__ uint32_t narrow(const float* f) {
+    f32x2 v;
+    v.x = f[0];
+    v.y = f[1];
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2));
+  }
   static __device__ __forceinline__ W add(W d, W s) {
-    const float r = (float)__builtin_bit_cast(_Float16, d) +
-                    (float)__builtin_bit_cast(_Float16, s);
-    return __builtin_bit_cast(W, (_Float16)r);
+    return down(up(d) + up(s));
   }
   static __device__ __forceinline__ uint32_t add32(uint32_t d, uint32_t s) {
-    const f32x2 r =
-        __builtin_convertvector(__builtin_bit_cast(f16x2, d), f32x2) +
-        __builtin_convertvector(__builtin_bit_cast(f16x2, s), f32x2);
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(r, f16x2));
+    float a[2], b[2];
+    widen(d, a);
+    widen(s, b);
+    a[0] += b[0];
+    a[1] += b[1];
+    return narrow(a);
   }
 };
 
 struct AccBF16 {
   using W = uint16_t;
+  static constexpr int kPerWord = 2;
   // A bf16 is the top half of an fp32: widening is a shift. The narrowing
   // conversion is the compiler's (v_cvt_pk_bf16_f32 on gfx950).
+  static __device__ __forceinline__ float up(W w) {
+    return __uint_as_float((uint32_t)w << 16);
+  }
+  static __device__ __forceinline__ W down(float f) {
+    return __builtin_bit_cast(W, (__bf16)f);
+  }
+  static __device__ __forceinline__ void widen(uint32_t w, float* f) {
+    f[0] = __uint_as_float(w << 16);
+    f[1] = __uint_as_float(w & 0xffff0000u);
+  }
+  static __device__ __forceinline__ uint32_t narrow(const float* f) {
+    f32x2 v;
+    v.x = f[0];
+    v.y = f[1];
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
+  }
   static __device__ __forceinline__ W add(W d, W s) {
-    const float r = __uint_as_float((uint32_t)d << 16) +
-                    __uint_as_float((uint32_t)s << 16);
-    return __builtin_bit_cast(W, (__bf16)r);
+    return down(up(d) + up(s));
   }
   static __device__ __forceinline__ uint32_t add32(uint32_t d, uint32_t s) {
-    f32x2 r;
-    r.x = __uint_as_float(d << 16) + __uint_as_float(s << 16);
-    r.y = __uint_as_float(d & 0xffff0000u) + __uint_as_float(s & 0xffff0000u);
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(r, bf16x2));
+    float a[2], b[2];
+    widen(d, a);
+    widen(s, b);
+    a[0] += b[0];
+    a[1] += b[1];
+    return narrow(a);
   }
 };
 
@@ -877,6 +927,301 @@ hipError_t launch_accum(void* dst, const void* src, size_t bytes,
     case ElemType::None: break;
   }
   return hipErrorInvalidValue;
+}
+
+// ---------------------------------------------------------------------------
+// Convert family (converting receive): the message holds one float type,
+// the buffer another. dst[i] = D(src[i]), or with ACC
+// dst[i] = D(float(dst[i]) + float(src[i])): every element goes through
+// fp32 and is rounded once, to nearest even; widening is exact. Exactly
+// msg.to(dtype) and (dst.float() + msg.float()).to(dtype). Subnormals are
+// kept, as in the accumulate family.
+//
+// Same shape as that family: 256-thread workgroups, grid stride, x4 unroll,
+// no LDS (nothing is reused). A lane takes E consecutive elements, whose
+// two sides differ in bytes for a 2-byte <-> 4-byte pair:
+//   E = 8 (shape A)  16 B on the narrow side, two adjacent 16 B accesses
+//                    on the wide side (a wave instruction then touches
+//                    every other 16 B of a 2 KiB window);
+//   E = 4 (shape B)  8 B on the narrow side, 16 B on the wide side, both
+//                    perfectly lane-contiguous.
+// fp16 <-> bf16 is 16 B to 16 B (E = 8) whatever the shape. Which of A and
+// B production runs, and the numbers behind it: kConvertProdShape.
+//
+// Source loads are plain. Whether non-temporal source loads pay off for
+// this byte ratio was not measured (the accumulate family's 192 MiB
+// crossover was measured for equal widths and does not carry over), so
+// there is no non-temporal variant and no threshold.
+// ---------------------------------------------------------------------------
+
+// NW 32-bit words at p: one 8 B access, or NW / 4 adjacent 16 B ones. p is
+// aligned to min(16, 4 * NW).
+template <int NW>
+__device__ __forceinline__ void ld_words(const uint8_t* p, uint32_t* w) {
+  if constexpr (NW == 2) {
+    const uint2 v = *(const uint2*)p;
+    w[0] = v.x;
+    w[1] = v.y;
+  } else {
+#pragma unroll
+    for (int q = 0; q < NW / 4; q++) {
+      const u32x4 v = *(const u32x4*)(p + 16 * q);
+      w[4 * q] = v.x;
+      w[4 * q + 1] = v.y;
+      w[4 * q + 2] = v.z;
+      w[4 * q + 3] = v.w;
+    }
+  }
+}
+template <int NW>
+__device__ __forceinline__ void st_words(const uint32_t* w, uint8_t* p) {
+  if constexpr (NW == 2) {
+    uint2 v;
+    v.x = w[0];
+    v.y = w[1];
+    *(uint2*)p = v;
+  } else {
+#pragma unroll
+    for (int q = 0; q < NW / 4; q++) {
+      u32x4 v;
+      v.x = w[4 * q];
+      v.y = w[4 * q + 1];
+      v.z = w[4 * q + 2];
+      v.w = w[4 * q + 3];
+      *(u32x4*)(p + 16 * q) = v;
+    }
+  }
+}
+
+// E elements of one lane: source words s, destination words d (read when
+// ACC, written always).
+template <class S, class D, bool ACC, int E>
+__device__ __forceinline__ void convert_lane(const uint32_t* s, uint32_t* d) {
+  float f[E];
+#pragma unroll
+  for (int j = 0; j < E / S::kPerWord; j++)
+    S::widen(s[j], &f[j * S::kPerWord]);
+  if constexpr (ACC) {
+    float g[E];
+#pragma unroll
+    for (int j = 0; j < E / D::kPerWord; j++)
+      D::widen(d[j], &g[j * D::kPerWord]);
+#pragma unroll
+    for (int e = 0; e < E; e++) f[e] = g[e] + f[e];
+  }
+#pragma unroll
+  for (int j = 0; j < E / D::kPerWord; j++)
+    d[j] = D::narrow(&f[j * D::kPerWord]);
+}
+
+// Vector bulk: nvec lanes' worth of E elements each. src is aligned to
+// min(16, E * sizeof(S::W)), dst to min(16, E * sizeof(D::W)). Offsets are
+// 64-bit: a message past 4 Gi elements addresses correctly.
+template <class S, class D, bool ACC, int E>
+__global__ __launch_bounds__(256) void k_convert_vec(
+    const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, size_t nvec) {
+  constexpr int SWN = E / S::kPerWord, DWN = E / D::kPerWord;
+  constexpr size_t SB = 4 * SWN, DB = 4 * DWN;  // bytes per lane, each side
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  // 4 (+ 4 when accumulating) independent loads in flight per thread.
+  while (i + 3 * stride < nvec) {
+    uint32_t s[4][SWN], d[4][DWN];
+#pragma unroll
+    for (int k = 0; k < 4; k++) ld_words<SWN>(src + (i + k * stride) * SB, s[k]);
+    if constexpr (ACC) {
+#pragma unroll
+      for (int k = 0; k < 4; k++)
+        ld_words<DWN>(dst + (i + k * stride) * DB, d[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      convert_lane<S, D, ACC, E>(s[k], d[k]);
+      st_words<DWN>(d[k], dst + (i + k * stride) * DB);
+    }
+    i += 4 * stride;
+  }
+  for (; i < nvec; i += stride) {
+    uint32_t s[SWN], d[DWN];
+    ld_words<SWN>(src + i * SB, s);
+    if constexpr (ACC) ld_words<DWN>(dst + i * DB, d);
+    convert_lane<S, D, ACC, E>(s, d);
+    st_words<DWN>(d, dst + i * DB);
+  }
+}
+
+// Element granularity: heads, tails and pairs no head can co-align. Both
+// pointers are aligned to their own element size.
+template <class S, class D, bool ACC>
+__global__ __launch_bounds__(256) void k_convert_elem(
+    const typename S::W* __restrict__ src, typename D::W* __restrict__ dst,
+    size_t n) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) {
+    float f = S::up(src[i]);
+    if constexpr (ACC) f = D::up(dst[i]) + f;
+    dst[i] = D::down(f);
+  }
+}
+
+// The lane shape production runs for a 2-byte <-> 4-byte pair: A. Measured
+// on MI355X, same-device loopback through the engine, both shapes
+// alternated in one process, us per receive, median of 9 rounds x 10 calls
+// (min-max over the rounds), two runs (docs/benchmark.md "Converting
+// receive", profiles/convert_bench_run*.jsonl); run 1:
+//   bf16 message += into fp32      shape A               shape B
+//     16 MiB                  48.4 (47.3-56.1)      45.4 (44.2-48.2)
+//     64 MiB                  84.5 (82.1-85.4)      82.8 (80.0-84.6)
+//     256 MiB                293.3 (289.8-296.5)   341.5 (335.4-347.3)
+//   fp32 message into bf16
+//     16 MiB                  36.3 (34.3-37.7)      36.0 (34.9-38.2)
+//     64 MiB                  47.7 (46.8-49.3)      48.1 (46.0-50.0)
+//     256 MiB                107.1 (103.3-109.7)   117.4 (114.3-122.5)
+// At 16 and 64 MiB the two are level (ranges overlap; B is ahead by 2-6 %
+// in the median for bf16 into fp32); at 256 MiB A takes 14 % and 9 % less
+// time with the ranges apart (16 % and 7 % in run 2). B stays built behind
+// ConvertShape::B (hooks only).
+constexpr ConvertShape kConvertProdShape = ConvertShape::A;
+
+// What ConvertShape::Default resolves to. Production never changes it; the
+// bench hook does, so one process can time both shapes through the engine.
+static std::atomic<ConvertShape> g_convert_shape{kConvertProdShape};
+
+ConvertShape convert_default_shape() {
+  return g_convert_shape.load(std::memory_order_relaxed);
+}
+void set_convert_default_shape(ConvertShape shape) {
+  g_convert_shape.store(
+      shape == ConvertShape::Default ? kConvertProdShape : shape,
+      std::memory_order_relaxed);
+}
+
+static int convert_lane_elems(ElemType dst_type, ElemType src_type,
+                              ConvertShape shape) {
+  if (shape == ConvertShape::Default) shape = convert_default_shape();
+  const bool mixed = elem_size(dst_type) != elem_size(src_type);
+  return mixed && shape == ConvertShape::B ? 4 : 8;
+}
+
+// Head of h elements, then whole lanes, then a tail. A lane's source access
+// is As = min(16, E * ss) bytes wide and its destination access
+// Ad = min(16, E * ds), so the bulk may start at element h only if
+//   (src + h * ss) % As == 0  and  (dst + h * ds) % Ad == 0.
+// Each side repeats with a period of As / ss and Ad / ds elements, both
+// powers of two. Solvable iff the two sides' element offsets from their own
+// boundary agree modulo the smaller period:
+//   (src / ss) % p == (dst / ds) % p,  p = min(As / ss, Ad / ds);
+// h is then the smallest solution, below the larger period (at most 7).
+// Otherwise the element kernel takes everything.
+ConvertPlan convert_plan(uintptr_t dst, ElemType dst_type, uintptr_t src,
+                         ElemType src_type, size_t n, ConvertShape shape) {
+  const size_t ss = elem_size(src_type), ds = elem_size(dst_type);
+  const size_t E = (size_t)convert_lane_elems(dst_type, src_type, shape);
+  const size_t as = E * ss < 16 ? E * ss : 16, ad = E * ds < 16 ? E * ds : 16;
+  const size_t ps = as / ss, pd = ad / ds;
+  ConvertPlan p{};
+  p.lane_elems = (int)E;
+  for (size_t h = 0; h < (ps > pd ? ps : pd); h++) {
+    if ((src + h * ss) % as || (dst + h * ds) % ad) continue;
+    p.head = h < n ? h : n;
+    p.vectors = (n - p.head) / E;
+    p.tail = (n - p.head) % E;
+    return p;
+  }
+  p.elem_only = true;
+  p.tail = n;
+  return p;
+}
+
+template <class S, class D>
+static hipError_t launch_convert_t(void* dst, const void* src, size_t n,
+                                   bool accumulate, const ConvertPlan& p,
+                                   hipStream_t stream, size_t cap) {
+  using SW = typename S::W;
+  using DW = typename D::W;
+  const SW* s = (const SW*)src;
+  DW* d = (DW*)dst;
+  auto elem = [&](const SW* es, DW* ed, size_t en, dim3 grid, dim3 block) {
+    if (accumulate)
+      hipLaunchKernelGGL((k_convert_elem<S, D, true>), grid, block, 0, stream,
+                         es, ed, en);
+    else
+      hipLaunchKernelGGL((k_convert_elem<S, D, false>), grid, block, 0,
+                         stream, es, ed, en);
+  };
+  if (p.elem_only) {
+    elem(s, d, n, dim3(copy_grid(n / 4 + 1, cap)), dim3(256));
+    return hipGetLastError();
+  }
+  if (p.head) elem(s, d, p.head, dim3(1), dim3(64));
+  s += p.head;
+  d += p.head;
+  if (p.vectors) {
+    const dim3 grid(copy_grid(p.vectors / 4 + 1, cap));
+    const uint8_t* sb = (const uint8_t*)s;
+    uint8_t* db = (uint8_t*)d;
+    auto vec = [&](auto e) {
+      constexpr int E = decltype(e)::value;
+      if (accumulate)
+        hipLaunchKernelGGL((k_convert_vec<S, D, true, E>), grid, dim3(256), 0,
+                           stream, sb, db, p.vectors);
+      else
+        hipLaunchKernelGGL((k_convert_vec<S, D, false, E>), grid, dim3(256), 0,
+                           stream, sb, db, p.vectors);
+    };
+    if constexpr (sizeof(SW) != sizeof(DW)) {
+      if (p.lane_elems == 4) vec(std::integral_constant<int, 4>{});
+      else vec(std::integral_constant<int, 8>{});
+    } else {
+      vec(std::integral_constant<int, 8>{});
+    }
+  }
+  if (p.tail)
+    elem(s + p.vectors * p.lane_elems, d + p.vectors * p.lane_elems, p.tail,
+         dim3(1), dim3(64));
+  return hipGetLastError();
+}
+
+// f(tag) for one of the three float types; false for anything else.
+template <class F>
+static bool with_float_tag(ElemType t, F&& f) {
+  switch (t) {
+    case ElemType::F32: f(AccF32{}); return true;
+    case ElemType::F16: f(AccF16{}); return true;
+    case ElemType::BF16: f(AccBF16{}); return true;
+    default: return false;
+  }
+}
+
+// dst and src must each be aligned to their own element size, the two types
+// must differ (equal types are launch_copy's and launch_accum's), and src
+// must not overlap dst.
+hipError_t launch_convert(void* dst, ElemType dst_type, const void* src,
+                          ElemType src_type, size_t n_elems, bool accumulate,
+                          hipStream_t stream, const CopyTuning& t) {
+  hipError_t result = hipErrorInvalidValue;
+  const bool known = with_float_tag(dst_type, [&](auto dtag) {
+    with_float_tag(src_type, [&](auto stag) {
+      using D = decltype(dtag);
+      using S = decltype(stag);
+      if constexpr (!std::is_same_v<S, D>) {
+        if ((uintptr_t)dst % sizeof(typename D::W) ||
+            (uintptr_t)src % sizeof(typename S::W))
+          return;
+        if (n_elems == 0) {
+          result = hipSuccess;
+          return;
+        }
+        const ConvertPlan p =
+            convert_plan((uintptr_t)dst, dst_type, (uintptr_t)src, src_type,
+                         n_elems, t.convert_shape);
+        result = launch_convert_t<S, D>(dst, src, n_elems, accumulate, p,
+                                        stream, t.block_cap);
+      }
+    });
+  });
+  return known ? result : hipErrorInvalidValue;
 }
 
 }  // namespace sw

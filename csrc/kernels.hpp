@@ -73,4 +73,22 @@ hipError_t launch_accum(void* dst, const void* src, size_t bytes,
                         ElemType dtype, hipStream_t stream,
                         const CopyTuning& t = default_copy_tuning());
 
+// Converting copy: dst[i] = dst_type(src[i]), or with `accumulate`
+// dst[i] = dst_type(float(dst[i]) + float(src[i])), over n_elems elements,
+// through fp32 and rounded once. The types are two different ones of F32,
+// F16, BF16; each pointer is aligned to its own element size; no overlap.
+// t.convert_shape picks the lane shape of a 2-byte <-> 4-byte pair.
+hipError_t launch_convert(void* dst, ElemType dst_type, const void* src,
+                          ElemType src_type, size_t n_elems, bool accumulate,
+                          hipStream_t stream,
+                          const CopyTuning& t = default_copy_tuning());
+// How launch_convert splits a message (ConvertPlan, copy_tuning.hpp).
+ConvertPlan convert_plan(uintptr_t dst, ElemType dst_type, uintptr_t src,
+                         ElemType src_type, size_t n_elems,
+                         ConvertShape shape = ConvertShape::Default);
+// What ConvertShape::Default resolves to: the production shape, unless a
+// bench has set another (Default sets it back). Host only.
+ConvertShape convert_default_shape();
+void set_convert_default_shape(ConvertShape shape);
+
 }  // namespace sw

@@ -51,6 +51,7 @@ static py::dict stats_dict(const Engine::Stats& st) {
   d["inbox_tx"] = st.inbox_tx.load();
   d["doorbell_rx"] = st.doorbell_rx.load();
   d["reduce_rx"] = st.reduce_rx.load();
+  d["cast_rx"] = st.cast_rx.load();
   d["index_tx"] = st.index_tx.load();
   d["index_rx"] = st.index_rx.load();
   return d;
@@ -69,16 +70,18 @@ static void bind_common(py::class_<T>& cls) {
       .def("recv",
            [](T& e, py::object buffer, uint64_t tag, uint64_t tag_mask,
               py::object done, py::object fail, const std::string& reduce,
-              const std::string& dtype, py::object index) {
+              const std::string& dtype, py::object index,
+              const std::string& msg_dtype) {
              BufferRef ref = parse_message_buffer(
-                 buffer, std::move(index), /*writable=*/true, reduce, dtype);
+                 buffer, std::move(index), /*writable=*/true, reduce, dtype,
+                 msg_dtype);
              e.engine.recv(ref, tag, tag_mask, std::move(done),
                            std::move(fail), std::move(buffer));
            },
            py::arg("buffer"), py::arg("tag"), py::arg("tag_mask"),
            py::arg("done_callback"), py::arg("fail_callback"),
            py::arg("reduce") = "", py::arg("dtype") = "",
-           py::arg("index") = py::none())
+           py::arg("index") = py::none(), py::arg("msg_dtype") = "")
       .def("flush",
            [](T& e, py::object done, py::object fail) {
              e.engine.flush(std::move(done), std::move(fail));

@@ -36,6 +36,31 @@ IndexWidth index_width(bool wide) {
   return wide ? IndexWidth::Wide : IndexWidth::Auto;
 }
 
+// shape of _convert_sync / _convert_plan / _convert_shape.
+ConvertShape parse_convert_shape(const char* what, const std::string& shape) {
+  if (shape.empty()) return ConvertShape::Default;
+  if (shape == "a") return ConvertShape::A;
+  if (shape == "b") return ConvertShape::B;
+  throw py::value_error(std::string(what) + ": shape must be 'a', 'b' or ''");
+}
+
+// (destination, source) types of the convert hooks: two different ones of
+// float32, float16, bfloat16.
+std::pair<ElemType, ElemType> convert_pair(const char* what,
+                                           const std::string& dst_dtype,
+                                           const std::string& src_dtype) {
+  const ElemType dt = parse_elem_type(dst_dtype);
+  const ElemType st = parse_elem_type(src_dtype);
+  for (const auto& [t, name] : {std::pair{dt, dst_dtype}, {st, src_dtype}})
+    if (t != ElemType::F32 && t != ElemType::F16 && t != ElemType::BF16)
+      throw py::value_error(std::string(what) + ": unsupported dtype '" +
+                            name + "'");
+  if (dt == st)
+    throw py::value_error(std::string(what) + ": the two dtypes are equal "
+                          "(that is _copy_device_sync's or _accum_sync's)");
+  return {dt, st};
+}
+
 // One side of _copy_index_sync: None for a dense side.
 IndexRef hook_index_side(py::object index, uint64_t slice_bytes,
                          uint64_t stride, bool writable) {
@@ -189,6 +214,73 @@ void bind_hooks(py::module_& m) {
         py::arg("dst"), py::arg("src"), py::arg("nbytes"), py::arg("dtype"),
         py::arg("device"), py::arg("block_cap") = 0,
         py::arg("nt_threshold") = 0);
+  // The convert kernels (converting receive): dst[i] = dst_dtype(src[i]),
+  // or with accumulate dst_dtype(float(dst[i]) + float(src[i])), over
+  // n_elems elements; two different types of float32, float16, bfloat16.
+  // shape: "a", "b" or "" (what production runs). The family has no
+  // non-temporal variant, so nt_threshold takes 0 only. Everything is
+  // checked before a device is touched.
+  m.def("_convert_sync",
+        [](uintptr_t dst, uintptr_t src, size_t n_elems,
+           const std::string& dst_dtype, const std::string& src_dtype,
+           int device, bool accumulate, size_t block_cap,
+           const std::string& shape, size_t nt_threshold) {
+          const auto [dt, st] = convert_pair("convert_sync", dst_dtype,
+                                             src_dtype);
+          if (dst % elem_size(dt) || src % elem_size(st))
+            throw py::value_error("convert_sync: each pointer must be a "
+                                  "multiple of its item size");
+          if (nt_threshold != 0)
+            throw py::value_error("convert_sync: the convert kernels have no "
+                                  "non-temporal variant (nt_threshold must "
+                                  "be 0)");
+          const CopyTuning tuning{
+              .block_cap = block_cap,
+              .convert_shape = parse_convert_shape("convert_sync", shape)};
+          released("convert_sync", gpu::convert_sync, (void*)dst, dt,
+                   (const void*)src, st, n_elems, accumulate, device, tuning);
+        },
+        py::arg("dst"), py::arg("src"), py::arg("n_elems"),
+        py::arg("dst_dtype"), py::arg("src_dtype"), py::arg("device"),
+        py::kw_only(), py::arg("accumulate") = false,
+        py::arg("block_cap") = 0, py::arg("shape") = "",
+        py::arg("nt_threshold") = 0);
+  // The split launch_convert makes of such a message: kernel "vector"
+  // (head, vectors of lane_elems elements, tail) or "element" (no head
+  // co-aligns the two sides; tail is everything). Host only.
+  m.def("_convert_plan",
+        [](uintptr_t dst, uintptr_t src, size_t n_elems,
+           const std::string& dst_dtype, const std::string& src_dtype,
+           const std::string& shape) {
+          const auto [dt, st] = convert_pair("convert_plan", dst_dtype,
+                                             src_dtype);
+          if (dst % elem_size(dt) || src % elem_size(st))
+            throw py::value_error("convert_plan: each pointer must be a "
+                                  "multiple of its item size");
+          const ConvertPlan p = gpu::convert_plan(
+              dst, dt, src, st, n_elems,
+              parse_convert_shape("convert_plan", shape));
+          py::dict d;
+          d["kernel"] = p.elem_only ? "element" : "vector";
+          d["lane_elems"] = p.lane_elems;
+          d["head"] = p.head;
+          d["vectors"] = p.vectors;
+          d["tail"] = p.tail;
+          return d;
+        },
+        py::arg("dst"), py::arg("src"), py::arg("n_elems"),
+        py::arg("dst_dtype"), py::arg("src_dtype"), py::arg("shape") = "");
+  // The lane shape production launches run ("a" or "b"). With an argument,
+  // a bench's override of it for this process ("" restores the production
+  // shape); returns the shape now in effect. Host only.
+  m.def("_convert_shape",
+        [](py::object shape) {
+          if (!shape.is_none())
+            gpu::set_convert_default_shape(parse_convert_shape(
+                "convert_shape", shape.cast<std::string>()));
+          return gpu::convert_default_shape() == ConvertShape::A ? "a" : "b";
+        },
+        py::arg("shape") = py::none());
   // descs: list of (dst, src, nbytes); one k_copy_multi launch.
   m.def("_copy_multi_sync",
         [](const std::vector<std::tuple<uintptr_t, uintptr_t, uint64_t>>&

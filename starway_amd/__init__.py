@@ -261,6 +261,55 @@ def _reduce_args(buffer: Any, reduce: str | None) -> dict:
     return {"reduce": reduce, "dtype": name}
 
 
+_MSG_DTYPES = ("float32", "float16", "bfloat16")
+
+
+def _msg_dtype_args(buffer: Any, msg_dtype: Any, index: Any = None) -> dict:
+    """Keyword arguments of the native recv for a converting receive.
+
+    ``msg_dtype`` (a ``torch.dtype`` or its name) declares the element type
+    of the MESSAGE; the buffer's own dtype stays that of the destination.
+    Delivery converts in the receiving kernel: ``buf[i] = msg[i]`` as
+    ``msg.to(buf.dtype)``, or with ``reduce="sum"``
+    ``(buf.float() + msg.float()).to(buf.dtype)``, over the first
+    ``length // msg_itemsize`` elements. Both are float32, float16 or
+    bfloat16; equal dtypes are the ordinary receive. The buffer must be a
+    contiguous device tensor aligned to its item size, and ``index=`` is
+    not allowed; each limit is a ValueError here, when the receive is
+    posted, whose text starts with ``msg_dtype limit:``. The name is
+    checked first, before the buffer is looked at.
+    """
+    if msg_dtype is None:
+        return {}
+    name = msg_dtype if isinstance(msg_dtype, str) else str(msg_dtype)
+    name = name.removeprefix("torch.")
+    if name not in _MSG_DTYPES:
+        raise ValueError(
+            f"msg_dtype limit: unsupported message dtype {name!r} "
+            f"(supported: {', '.join(_MSG_DTYPES)})")
+    if index is not None:
+        raise ValueError("msg_dtype limit: index= cannot be combined with "
+                         "msg_dtype= (a converting destination stays "
+                         "contiguous)")
+    own = None
+    if type(buffer).__module__.startswith("torch"):
+        if buffer.is_cuda:
+            own = str(buffer.dtype).removeprefix("torch.")
+    elif hasattr(buffer, "__cuda_array_interface__"):
+        typestr = buffer.__cuda_array_interface__["typestr"]
+        own = _TYPESTR_DTYPES.get(typestr[1:], typestr)
+    if own is None:
+        raise ValueError("msg_dtype limit: host buffers are not supported "
+                         "(device tensors only)")
+    if own not in _MSG_DTYPES:
+        raise ValueError(
+            f"msg_dtype limit: unsupported buffer dtype {own!r} "
+            f"(supported: {', '.join(_MSG_DTYPES)})")
+    if own == name:
+        return {}
+    return {"msg_dtype": name, "dtype": own}
+
+
 class Server:
     def __init__(self) -> None:
         self._server = _Server(_context)
@@ -302,9 +351,11 @@ class Server:
         )
 
     def recv(self, buffer, tag, tag_mask, done_callback, fail_callback, *,
-             reduce: str | None = None, index=None):
+             reduce: str | None = None, index=None, msg_dtype=None):
+        cast = _msg_dtype_args(buffer, msg_dtype, index)
         buf, kw = _index_args(buffer, index, reduce)
         kw.update(_reduce_args(buffer, reduce))
+        kw.update(cast)
         return self._server.recv(
             buf, tag, tag_mask, done_callback, fail_callback, **kw
         )
@@ -337,13 +388,17 @@ class Server:
 
     def arecv(self, buffer, tag: int, tag_mask: int,
               loop: asyncio.AbstractEventLoop | None = None, *,
-              reduce: str | None = None, index=None):
+              reduce: str | None = None, index=None, msg_dtype=None):
         """Post a receive. ``reduce="sum"`` makes it a reducing receive
         (see ``_reduce_args``): the message is added into the buffer.
         ``index=idx`` writes message slice ``r`` to ``buffer[idx[r]]`` (see
-        ``_index_args``)."""
+        ``_index_args``). ``msg_dtype=`` declares the element type of the
+        message when it differs from the buffer's: a converting receive
+        (see ``_msg_dtype_args``)."""
+        cast = _msg_dtype_args(buffer, msg_dtype, index)
         buf, kw = _index_args(buffer, index, reduce)
         kw.update(_reduce_args(buffer, reduce))
+        kw.update(cast)
         if loop is None:
             loop = asyncio.get_running_loop()
         ret: asyncio.Future[tuple[int, int]] = asyncio.Future(loop=loop)
@@ -445,9 +500,11 @@ class Client:
         return self._client.send(buf, tag, done_callback, fail_callback, **kw)
 
     def recv(self, buffer, tag, tag_mask, done_callback, fail_callback, *,
-             reduce: str | None = None, index=None):
+             reduce: str | None = None, index=None, msg_dtype=None):
+        cast = _msg_dtype_args(buffer, msg_dtype, index)
         buf, kw = _index_args(buffer, index, reduce)
         kw.update(_reduce_args(buffer, reduce))
+        kw.update(cast)
         return self._client.recv(
             buf, tag, tag_mask, done_callback, fail_callback, **kw
         )
@@ -477,13 +534,17 @@ class Client:
 
     def arecv(self, buffer, tag: int, tag_mask: int,
               loop: asyncio.AbstractEventLoop | None = None, *,
-              reduce: str | None = None, index=None):
+              reduce: str | None = None, index=None, msg_dtype=None):
         """Post a receive. ``reduce="sum"`` makes it a reducing receive
         (see ``_reduce_args``): the message is added into the buffer.
         ``index=idx`` writes message slice ``r`` to ``buffer[idx[r]]`` (see
-        ``_index_args``)."""
+        ``_index_args``). ``msg_dtype=`` declares the element type of the
+        message when it differs from the buffer's: a converting receive
+        (see ``_msg_dtype_args``)."""
+        cast = _msg_dtype_args(buffer, msg_dtype, index)
         buf, kw = _index_args(buffer, index, reduce)
         kw.update(_reduce_args(buffer, reduce))
+        kw.update(cast)
         if loop is None:
             loop = asyncio.get_running_loop()
         ret: asyncio.Future[tuple[int, int]] = asyncio.Future(loop=loop)

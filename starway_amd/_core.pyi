@@ -52,11 +52,22 @@ class Server:
         reduce: str = "",
         dtype: str = "",
         index: Index | None = None,
+        msg_dtype: str = "",
     ) -> None:
         """reduce="sum" with dtype float32 / float16 / bfloat16 / int32: a
         reducing receive, buf[i] += msg[i] over length // itemsize elements.
         ValueError for an unknown op, a host buffer, another dtype, a
         non-contiguous destination or one not aligned to its item size.
+
+        msg_dtype (float32 / float16 / bfloat16) with dtype, the buffer's
+        own, another of the three: a converting receive. The message is
+        read as msg_dtype elements and converted in the kernel, buf[i] =
+        dtype(msg[i]), or with reduce="sum" dtype(float(buf[i]) +
+        float(msg[i])), over length // msg_itemsize elements. Equal names
+        are the receive without msg_dtype. ValueError starting "msg_dtype
+        limit:" for another name (checked before the buffer is looked at),
+        a host buffer, another buffer dtype, a non-contiguous or
+        item-misaligned destination, or index= with msg_dtype=.
 
         index=idx: message slice r is written to buffer[idx[r]]. The buffer
         is a device tensor exporting its own shape and byte strides, dense
@@ -109,11 +120,22 @@ class Client:
         reduce: str = "",
         dtype: str = "",
         index: Index | None = None,
+        msg_dtype: str = "",
     ) -> None:
         """reduce="sum" with dtype float32 / float16 / bfloat16 / int32: a
         reducing receive, buf[i] += msg[i] over length // itemsize elements.
         ValueError for an unknown op, a host buffer, another dtype, a
         non-contiguous destination or one not aligned to its item size.
+
+        msg_dtype (float32 / float16 / bfloat16) with dtype, the buffer's
+        own, another of the three: a converting receive. The message is
+        read as msg_dtype elements and converted in the kernel, buf[i] =
+        dtype(msg[i]), or with reduce="sum" dtype(float(buf[i]) +
+        float(msg[i])), over length // msg_itemsize elements. Equal names
+        are the receive without msg_dtype. ValueError starting "msg_dtype
+        limit:" for another name (checked before the buffer is looked at),
+        a host buffer, another buffer dtype, a non-contiguous or
+        item-misaligned destination, or index= with msg_dtype=.
 
         index=idx: message slice r is written to buffer[idx[r]]. The buffer
         is a device tensor exporting its own shape and byte strides, dense
@@ -155,6 +177,35 @@ def _accum_sync(
     source loads are non-temporal; 0 = the process default, 192 MiB).
     ValueError for another dtype, or pointers / a length that are not
     multiples of the item size."""
+
+def _convert_sync(
+    dst: int, src: int, n_elems: int, dst_dtype: str, src_dtype: str,
+    device: int, *, accumulate: bool = False, block_cap: int = 0,
+    shape: str = "", nt_threshold: int = 0,
+) -> None:
+    """Run the convert kernels (k_convert_vec / k_convert_elem)
+    synchronously on raw device pointers: dst[i] = dst_dtype(src[i]), or
+    with accumulate dst_dtype(float(dst[i]) + float(src[i])), over n_elems
+    elements. The dtypes are two different ones of float32, float16,
+    bfloat16. shape picks the lane shape of a 2-byte <-> 4-byte pair: "a"
+    (8 elements per lane), "b" (4) or "" (what production runs). The family
+    has no non-temporal variant: nt_threshold takes 0 only. ValueError,
+    before any device is touched, for anything else, equal dtypes or a
+    pointer that is not a multiple of its item size."""
+
+def _convert_plan(
+    dst: int, src: int, n_elems: int, dst_dtype: str, src_dtype: str,
+    shape: str = "",
+) -> dict[str, Any]:
+    """How the convert dispatch splits such a message: kernel ("vector" or
+    "element"), lane_elems, head, vectors, tail. "element" means no head
+    co-aligns the two sides and the element kernel takes all n_elems
+    (reported as tail). Host only."""
+
+def _convert_shape(shape: str | None = None) -> str:
+    """The lane shape ("a" or "b") that shape="" resolves to: the
+    production shape, unless a bench has set another with this call (""
+    restores it). Host only."""
 
 def _copy_tuning() -> dict[str, int]: ...
 def _copy_stream_tuning() -> dict[str, int]:
